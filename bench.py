@@ -6,15 +6,26 @@ framework's ``KMeansTrainBatchOp`` BSP queue: fused HIP assign+accumulate over t
 all-reduce of the [k, d+1] sums, centroid update and the convergence criterion.  The 1e8-row table is fixed
 (strong scaling: each of N ranks holds 1e8/N rows, generated on its own GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--k 100] [--dims 128]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--k 100] [--dims 128] [--full]
+                    [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: it generates the table, runs W warm-up and K timed
+supersteps, and prints the result line.  ``--full`` adds everything else described below (the untimed convergence
+runs, the SSE of the timed run's model, the clock / power telemetry); without it those fields are null / empty.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the timed training returned to its caller, i.e. the model
+after the last timed superstep, as ``DIR/centroids.npy`` ([k, d] float64) and ``DIR/weights.npy`` ([k] float64,
+rows per cluster).  The table and the initialisation are seeded, so two runs with the same arguments see the same
+inputs.
 
 ``--gpus N`` without a launcher around it starts the N ranks itself (``alink_amd/parallel/launch.py``: N
 child processes with RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set, started before this process touches the
 GPU; rank 0's JSON line is the job's output; a failing or hung rank fails the job).
 
 Prints ONE JSON line on rank 0.  ``value`` = total rows processed per second by the whole job
-(rows x K / max-over-ranks elapsed).  Also reports ``iters_to_converge`` from a separate untimed run with
+(rows x K / max-over-ranks elapsed), ``ms_per_step`` = that elapsed time / K in milliseconds.  With ``--full`` it
+also reports ``iters_to_converge`` from a separate untimed run with
 epsilon 1e-4 at the reference defaults (k-means|| initSteps=2 and the reference's sampled k-means++ seeding over
 the candidates, ``convergence.reference``), plus the opt-in greedy seeding (``convergence.greedy``) and
 initSteps=5 for comparison; every run reports its final SSE (sum of squared distances to the nearest centroid)
@@ -32,8 +43,8 @@ per timed superstep (HIP events around the fused kernel and its slab reduction),
 per-rank values and ``straggler_ms_per_step`` their spread — so a multi-GPU step time splits into the slowest
 rank's kernel, the wait for it (inside ``allreduce_us_per_step``) and the collective itself.
 
-Telemetry (``--telemetry 1``, default on a GPU): an ``amdsmi`` sampling process (``alink_amd/utils/telemetry.py``)
-records gfx / memory clocks, socket power and temperatures every 5 ms; ``telemetry`` holds per-phase min / median /
+Telemetry (``--telemetry 1``, the default of a ``--full`` run on a GPU): an ``amdsmi`` sampling process
+(``alink_amd/utils/telemetry.py``) records gfx / memory clocks, socket power and temperatures every 5 ms; ``telemetry`` holds per-phase min / median /
 max (data generation, warm-up, timed window, convergence runs) and the throttle-residency deltas of rank 0, plus
 every rank's timed-window medians.  ``ALINK_TELEMETRY_OUT=path`` also writes rank 0's raw series there.
 """
@@ -71,6 +82,16 @@ def _sse(data, op, dev) -> float:
     return float(t.item())
 
 
+def _dump_outputs(out_dir, op) -> None:
+    """The model rows ``op`` returned, decoded: ``centroids.npy`` [k, d] and ``weights.npy`` [k], both float64."""
+    import numpy as np
+    from alink_amd.models.clustering.kmeans import KMeansModelDataConverter
+    md = KMeansModelDataConverter().load(op.collect())
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "centroids.npy"), np.ascontiguousarray(md.centroids, dtype=np.float64))
+    np.save(os.path.join(out_dir, "weights.npy"), np.ascontiguousarray(md.weights, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -79,14 +100,27 @@ def main():
     ap.add_argument("--rows", type=int, default=100_000_000)
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--dims", type=int, default=128)
-    ap.add_argument("--converge-iters", type=int, default=100, help="maxIter of the convergence run (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the convergence runs, the SSE of the "
+                         "timed run's model and the telemetry sampler")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the model of the last timed superstep as DIR/centroids.npy and DIR/weights.npy")
+    ap.add_argument("--converge-iters", type=int, default=100,
+                    help="--full: maxIter of the convergence run (0 = skip)")
     ap.add_argument("--timeout", type=float, default=1500.0, help="self-launched job time limit (s)")
     ap.add_argument("--convergence-first", type=int, default=0,
                     help="1: the untimed convergence runs before the timed run (0: after it)")
-    ap.add_argument("--telemetry", type=int, default=1, help="1: sample GPU clocks / power (amdsmi) during the run")
+    ap.add_argument("--telemetry", type=int, default=None,
+                    help="1: sample GPU clocks / power (amdsmi) during the run (default: 1 with --full, else 0)")
     ap.add_argument("--kernel-timing", type=int, default=1,
                     help="1: HIP events around every assign launch in the window (per-rank kernel time fields)")
     a = ap.parse_args()
+    if a.telemetry is None:
+        a.telemetry = int(a.full)
+    if a.warmup < 1:
+        raise SystemExit("--warmup must be >= 1 (the first superstep includes one-time setup)")
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # self-launch: this parent never initialises the GPU; each child is one rank (one MI355X)
@@ -132,7 +166,7 @@ def main():
         iters, conv = None, {}
         # ---- convergence runs (epsilon 1e-4): the reference defaults (k-means|| initSteps=2, the reference's sampled
         # k-means++ seeding over the candidates), the opt-in greedy seeding, and initSteps=5 ----
-        if a.converge_iters > 0:
+        if a.full and a.converge_iters > 0:
             for tag, steps, seeding in (("reference", 2, "reference"), ("greedy", 2, "greedy"),
                                         ("initSteps5", 5, "reference")):
                 old = os.environ.get("ALINK_KMEANS_SEEDING")
@@ -194,8 +228,6 @@ def main():
     op.linkFrom(TableSourceBatchOp(data))
     hip_used = kops.HIP_CALLS > hip0
     t_tot = time.perf_counter() - t_tot
-    if a.warmup == 0:
-        raise SystemExit("--warmup must be >= 1 (the first superstep includes one-time setup)")
     elapsed = marks[a.warmup + a.steps] - marks[a.warmup]
     el = torch.tensor([elapsed], dtype=torch.float64)
     n_ev, dev_comm_s, _ = comm.device_timing_collect()
@@ -213,7 +245,9 @@ def main():
     stats = op._queue.stats[a.warmup:a.warmup + a.steps]
     live_k = int(op._queue.final_contexts[0].getObj("k"))
     comm_bytes = sum(s["comm_bytes"] for s in stats) / max(1, len(stats))
-    timed_sse = _sse(data, op, dev)
+    if a.dump_outputs and env.rank == 0:
+        _dump_outputs(a.dump_outputs, op)
+    timed_sse = _sse(data, op, dev) if a.full else None
 
     if not a.convergence_first:
         iters, conv = convergence_runs()
@@ -248,6 +282,7 @@ def main():
         "unit": "rows/s",
         "n_gpus": env.world_size,
         "steps": a.steps,
+        "full": bool(a.full),
         "warmup": a.warmup,
         "ms_per_step": elapsed / a.steps * 1e3,
         "higher_is_better": True,

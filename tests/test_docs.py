@@ -4,8 +4,6 @@ import os
 import subprocess
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -19,7 +17,6 @@ def test_every_exported_op_documented():
     assert len(ops) >= 450
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/docs/en"), reason="reference docs not present")
 def test_docs_in_sync():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_docs.py"), "--check"], capture_output=True,
                        text=True, timeout=300)

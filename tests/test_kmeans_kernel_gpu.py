@@ -668,8 +668,7 @@ def test_v10_l2_prefetch_identical():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     lib = os.path.join(root, "variants", "libalink_hip_pfd.so")
-    if not os.path.exists(lib):
-        pytest.skip("variants/libalink_hip_pfd.so not built (tools/build_kmeans_variants.sh pfd)")
+    assert os.path.exists(lib), "variants/libalink_hip_pfd.so not built (python build_native.py)"
     env = dict(os.environ, ALINK_HIP_LIB=lib, PYTHONPATH=root)
     r = subprocess.run([sys.executable, "-c", "import tests.test_kmeans_kernel_gpu as t; t._pfd_identity_check()"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=110)

@@ -79,7 +79,7 @@ def test_bench_self_launches_n_ranks():
 def test_bench_self_launches_eight_ranks_like_the_driver():
     """The driver's 8-GPU shape of the headline bench (N=8, strong scaling), rehearsed on the CPU: 8 ranks, a row
     count that does not divide by 8, the convergence run included; every rank holds its share of the rows."""
-    res = _bench(8, ["--rows", "40003", "--converge-iters", "20"])
+    res = _bench(8, ["--rows", "40003", "--full", "--converge-iters", "20"])
     assert res["n_gpus"] == 8 and res["config"]["parallelism"] == "dp8"
     assert res["effective_config"]["rows_per_rank"] == 40003 // 8
     # straggler split: every rank's timed assign time, max / min / spread consistent with them
@@ -91,6 +91,24 @@ def test_bench_self_launches_eight_ranks_like_the_driver():
     assert res["telemetry"]["available"] is False
     assert res["allreduce_bytes_per_step"] == res["live_k"] * (128 + 1) * 8
     assert 1 <= res["iters_to_converge"] <= 20 and res["convergence"]["reference"]["sse"] > 0
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    """A plain run skips what ``--full`` adds, and ``--dump-outputs`` writes the timed run's model: the same
+    arguments give the same inputs, so two runs agree output for output."""
+    outs = []
+    for tag in ("a", "b"):
+        res = _bench(1, ["--rows", "4001", "--dump-outputs", str(tmp_path / tag)])
+        assert res["steps"] == 2 and res["ms_per_step"] > 0 and res["full"] is False
+        assert abs(res["value"] - 4001 * 2 / (res["ms_per_step"] * 2e-3)) <= 1e-6 * res["value"]
+        assert res["iters_to_converge"] is None and res["convergence"] == {} and res["sse_timed_run"] is None
+        assert sorted(os.listdir(tmp_path / tag)) == ["centroids.npy", "weights.npy"]
+        C, w = np.load(tmp_path / tag / "centroids.npy"), np.load(tmp_path / tag / "weights.npy")
+        assert C.dtype == np.float64 and C.shape == (res["live_k"], 128)
+        assert w.dtype == np.float64 and w.shape == (res["live_k"],) and w.sum() == 4001
+        outs.append((C, w))
+    np.testing.assert_array_equal(outs[0][1], outs[1][1])
+    np.testing.assert_allclose(outs[0][0], outs[1][0], rtol=0, atol=1e-9)
 
 
 def test_bench_rejects_mismatched_world():
