@@ -239,20 +239,15 @@ def _seed_reference_device(D: torch.Tensor, w: torch.Tensor, k: int, rng, idx0: 
     n = D.shape[0]
     state = rng.bit_generator.state
     U = torch.as_tensor(rng.random(k - 1), dtype=torch.float64, device=D.device)
-    chosen = torch.empty(k, dtype=torch.int64, device=D.device)
-    mintot = torch.full((1,), float("inf"), dtype=torch.float64, device=D.device)
     if D.is_cuda and n <= 4096 and _lib.available():
         # all k-1 picks in one single-workgroup launch (csrc/kmeans_nearest.hip kmeans_seed_ref_kernel)
-        L = _lib.require()
-        Dc, wc = D.contiguous(), w.contiguous()
-        rc = L.alink_kmeans_seed_ref(Dc.data_ptr(), wc.data_ptr(), U.data_ptr(), n, k, int(idx0), chosen.data_ptr(),
-                                     mintot.data_ptr(), _lib.stream_ptr(D.device))
-        if rc != 0:
-            raise RuntimeError(f"alink_kmeans_seed_ref failed: {rc}")
+        chosen, mintot = kops.seed_ref_hip(D, w, U, k, idx0=idx0)
         if not float(mintot.item()) > 0:
             rng.bit_generator.state = state
             return None
         return chosen
+    chosen = torch.empty(k, dtype=torch.int64, device=D.device)
+    mintot = torch.full((1,), float("inf"), dtype=torch.float64, device=D.device)
     chosen[0] = idx0
     costs = D[idx0].clone()
     for j in range(1, k):
@@ -498,73 +493,83 @@ class KMeansUpdateCentroids(ComputeFunction):
         tgt = ctx.getObj(CENTROID2) if ctx.getStepNo() % 2 == 0 else ctx.getObj(CENTROID1)
         old = ctx.getObj(CENTROID1) if ctx.getStepNo() % 2 == 0 else ctx.getObj(CENTROID2)
         buf = ctx.getObj(CENTROID_ALL_REDUCE)
-        d = buf.shape[1] - 1
-        cnt = buf[:, d]
         prev = old[1] if old is not None and old[1] is not None else None
         if self.dist_type == "EUCLIDEAN" and kops.update_supported(buf) and \
                 (_lib_ok() or not kops._lib.torch_fallback_allowed()):
-            # fused HIP update: C, the shift vs prev, the empty flag and the next step's MFMA operands in one
-            # launch + one 16-byte read
-            step = ctx.getStepNo()
-            X = ctx.getObj(TRAIN_DATA)
-            spec_ok = (self.speculate and step >= 2 and step < self.max_iter and step not in self.sync_steps
-                       and X is not None and X.shape[0] > 0 and kops.hip_supported(X, buf.shape[0]))
-            C, read = kops.update_centroids_hip(buf, prev, deferred=True,
-                                                skip_tol=self.tol if spec_ok and self.tol is not None else None)
-            if spec_ok:
-                ctx.putObj(SPEC_BUF, ((step + 1, kops._ckey(C)),
-                                      kops.assign_accumulate_hip(X, C, reverse=kops.serpentine_reverse(step + 1),
-                                                                 skip=read.skip)))
-            shift, has_empty = read()
-            if has_empty or (read.skip is not None and shift is not None and shift < self.tol):
-                ctx.removeObj(SPEC_BUF)     # not used (compaction) / possibly skipped on the device (converged)
+            C, shift, has_empty = self._fused_update(ctx, buf, prev)
+            weights = buf[:, -1]
             if has_empty:
-                # drop the empty clusters on the host (k x 129 values): the fused update's C rows are the same
-                # fp64 quotients the generic path computes, and the rare path issues no torch kernel that the
-                # supersteps do not already use (a first use of e.g. norm / nonzero costs a lazy code-object load,
-                # ~100 ms, inside the first job's supersteps)
-                # one stream sync for all three reads (async copies into pinned buffers), one H2D copy back
-                kk, dd = C.shape
-                use_prev = prev is not None and prev.shape[1] == dd and prev.dtype == C.dtype
-                pin = C.is_cuda
-                h_cnt = torch.empty(cnt.shape, dtype=cnt.dtype, pin_memory=pin)
-                h_C = torch.empty(C.shape, dtype=C.dtype, pin_memory=pin)
-                h_prev = torch.empty((min(prev.shape[0], kk) if use_prev else 0, dd), dtype=C.dtype, pin_memory=pin)
-                h_cnt.copy_(cnt, non_blocking=pin)
-                h_C.copy_(C, non_blocking=pin)
-                if use_prev:
-                    h_prev.copy_(prev[:h_prev.shape[0]], non_blocking=pin)
-                if pin:
-                    torch.cuda.current_stream(C.device).synchronize()
-                cnt_h = h_cnt.numpy()
-                keep = np.flatnonzero(cnt_h > 0)
-                C_h = h_C.numpy()[keep]
-                # the criterion's shift (first k rows of the previous centroids vs the new ones), on the host too
-                shift_h = None
-                if use_prev and h_prev.shape[0] >= len(keep):
-                    dlt = h_prev.numpy()[:len(keep)] - C_h
-                    shift_h = float(np.sqrt((dlt * dlt).sum(1)).max()) if len(keep) else None
-                # the kept centroids and their weights in one pinned block -> one copy; C / weights are views of it
-                kk2 = len(keep)
-                h_pack = torch.empty(kk2 * dd + kk2, dtype=C.dtype, pin_memory=pin)
-                hp = h_pack.numpy()
-                hp[:kk2 * dd] = C_h.reshape(-1)
-                hp[kk2 * dd:] = cnt_h[keep]
-                pack = h_pack.to(C.device, non_blocking=pin)
-                C = pack[:kk2 * dd].view(kk2, dd)
-                ctx.putObj("maxShift", shift_h)
-                tgt[0] = ctx.getStepNo()
-                tgt[1] = C
-                ctx.putObj("lastWeights", pack[kk2 * dd:].to(cnt.dtype))
-                ctx.putObj(K, int(C.shape[0]))
-                return
-            if not has_empty:
-                ctx.putObj("maxShift", shift)
-                tgt[0] = ctx.getStepNo()
-                tgt[1] = C
-                ctx.putObj("lastWeights", cnt)
-                ctx.putObj(K, int(C.shape[0]))
-                return
+                C, weights, shift = self._compact_on_host(C, weights, prev)
+        else:
+            C, weights, shift = self._torch_update(buf, prev)
+        self._publish(ctx, tgt, C, weights, shift)
+
+    @staticmethod
+    def _publish(ctx, tgt, C, weights, shift):
+        ctx.putObj("maxShift", shift)
+        tgt[0] = ctx.getStepNo()
+        tgt[1] = C
+        ctx.putObj("lastWeights", weights)
+        ctx.putObj(K, int(C.shape[0]))
+
+    def _fused_update(self, ctx, buf, prev):
+        """Fused HIP update: C, the shift vs prev, the empty flag and the next step's MFMA operands in one launch +
+        one 16-byte read; the next superstep's assign kernel is queued between the launch and the read."""
+        step = ctx.getStepNo()
+        X = ctx.getObj(TRAIN_DATA)
+        spec_ok = (self.speculate and step >= 2 and step < self.max_iter and step not in self.sync_steps
+                   and X is not None and X.shape[0] > 0 and kops.hip_supported(X, buf.shape[0]))
+        C, read = kops.update_centroids_hip(buf, prev, deferred=True,
+                                            skip_tol=self.tol if spec_ok and self.tol is not None else None)
+        if spec_ok:
+            ctx.putObj(SPEC_BUF, ((step + 1, kops._ckey(C)),
+                                  kops.assign_accumulate_hip(X, C, reverse=kops.serpentine_reverse(step + 1),
+                                                             skip=read.skip)))
+        shift, has_empty = read()
+        if has_empty or (read.skip is not None and shift is not None and shift < self.tol):
+            ctx.removeObj(SPEC_BUF)     # not used (compaction) / possibly skipped on the device (converged)
+        return C, shift, has_empty
+
+    @staticmethod
+    def _compact_on_host(C, cnt, prev):
+        """Drop the empty clusters of the fused update's result on the host (k x 129 values): its C rows are the
+        same fp64 quotients the generic path computes, and the rare path issues no torch kernel that the
+        supersteps do not already use (a first use of e.g. norm / nonzero costs a lazy code-object load, ~100 ms,
+        inside the first job's supersteps).  Returns (C, weights, shift) of the kept clusters."""
+        # one stream sync for all three reads (async copies into pinned buffers), one H2D copy back
+        kk, dd = C.shape
+        use_prev = prev is not None and prev.shape[1] == dd and prev.dtype == C.dtype
+        pin = C.is_cuda
+        h_cnt = torch.empty(cnt.shape, dtype=cnt.dtype, pin_memory=pin)
+        h_C = torch.empty(C.shape, dtype=C.dtype, pin_memory=pin)
+        h_prev = torch.empty((min(prev.shape[0], kk) if use_prev else 0, dd), dtype=C.dtype, pin_memory=pin)
+        h_cnt.copy_(cnt, non_blocking=pin)
+        h_C.copy_(C, non_blocking=pin)
+        if use_prev:
+            h_prev.copy_(prev[:h_prev.shape[0]], non_blocking=pin)
+        if pin:
+            torch.cuda.current_stream(C.device).synchronize()
+        cnt_h = h_cnt.numpy()
+        keep = np.flatnonzero(cnt_h > 0)
+        C_h = h_C.numpy()[keep]
+        # the criterion's shift (first k rows of the previous centroids vs the new ones), on the host too
+        shift_h = None
+        if use_prev and h_prev.shape[0] >= len(keep):
+            dlt = h_prev.numpy()[:len(keep)] - C_h
+            shift_h = float(np.sqrt((dlt * dlt).sum(1)).max()) if len(keep) else None
+        # the kept centroids and their weights in one pinned block -> one copy; C / weights are views of it
+        kk2 = len(keep)
+        h_pack = torch.empty(kk2 * dd + kk2, dtype=C.dtype, pin_memory=pin)
+        hp = h_pack.numpy()
+        hp[:kk2 * dd] = C_h.reshape(-1)
+        hp[kk2 * dd:] = cnt_h[keep]
+        pack = h_pack.to(C.device, non_blocking=pin)
+        return pack[:kk2 * dd].view(kk2, dd), pack[kk2 * dd:].to(cnt.dtype), shift_h
+
+    def _torch_update(self, buf, prev):
+        """Generic update: (C, weights, shift) with the empty clusters dropped (then no shift)."""
+        d = buf.shape[1] - 1
+        cnt = buf[:, d]
         # ONE small D2H read per superstep: the (rare) empty-cluster flag together with the max centroid shift
         # the termination criterion needs (the criterion then reads the host float instead of syncing again)
         C = buf[:, :d] / cnt[:, None]
@@ -576,26 +581,10 @@ class KMeansUpdateCentroids(ComputeFunction):
             flag, shift = torch.stack([empty_any, (C - prev).norm(dim=1).max()]).tolist()
         else:
             flag = empty_any.item()
-        empty = (cnt <= 0).nonzero().reshape(-1).tolist() if flag > 0 else []
-        ctx.putObj("maxShift", None if empty else shift)
-        if not empty:
-            tgt[0] = ctx.getStepNo()
-            tgt[1] = C
-            ctx.putObj("lastWeights", cnt)
-            ctx.putObj(K, int(C.shape[0]))
-            return
-        if empty:
-            keep = torch.as_tensor([i for i in range(buf.shape[0]) if i not in set(empty)], dtype=torch.long,
-                                   device=buf.device)
-            buf = buf.index_select(0, keep)
-            cnt = buf[:, d]
-        C = buf[:, :d] / cnt[:, None]
-        if self.dist_type == "COSINE":
-            C = _normalize_rows(C)
-        tgt[0] = ctx.getStepNo()
-        tgt[1] = C
-        ctx.putObj("lastWeights", cnt)
-        ctx.putObj(K, int(C.shape[0]))
+        if flag > 0:
+            keep = (cnt <= 0).logical_not().nonzero().reshape(-1)
+            C, cnt, shift = C.index_select(0, keep), cnt.index_select(0, keep), None
+        return C, cnt, shift
 
 
 class KMeansIterTermination(CompareCriterionFunction):

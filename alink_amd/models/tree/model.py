@@ -460,8 +460,7 @@ class _DeviceForest:
         ct = torch.uint8 if self.code_bytes == 1 else torch.int16
         miss = 255 if self.code_bytes == 1 else -1              # 0xFFFF as int16
         if use_kernel is None:
-            use_kernel = torch.device(self.dev).type == "cuda" and _lib.available() and \
-                hasattr(_lib.require(), "alink_tree_codes")
+            use_kernel = torch.device(self.dev).type == "cuda" and _lib.available()
         if use_kernel:
             L = _lib.require()
             out = torch.empty((n, self.stride // self.code_bytes), dtype=ct, device=self.dev)
@@ -613,11 +612,9 @@ class TreeModelMapper(RichModelMapper):
         acc = torch.empty((n, dfo.nd), dtype=torch.float64, device=dev)
         wacc = torch.empty(n, dtype=torch.float64, device=dev)
         err = torch.zeros(1, dtype=torch.int32, device=dev)
-        # codes are built per chunk of rows (the batched searchsorted holds [features, rows] int64 temporaries)
-        # the device code kernel needs only the [chunk, stride] code block (1 GiB of rows at a time); the torch form
-        # holds [features, rows] int64 temporaries
-        chunk = max(64, ((1 << 30) // dfo.stride) // 64 * 64) if hasattr(L, "alink_tree_codes") else \
-            max(64, ((1 << 27) // max(1, len(dfo.slot))) // 64 * 64)
+        # codes are built per chunk of rows: the device code kernel needs only the [chunk, stride] code block (1 GiB
+        # of rows at a time)
+        chunk = max(64, ((1 << 30) // dfo.stride) // 64 * 64)
         for lo in range(0, n, chunk):
             hi = min(n, lo + chunk)
             codes = dfo.codes(cols, cats, hi - lo, row0=lo)

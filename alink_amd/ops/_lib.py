@@ -15,7 +15,7 @@ from typing import Optional
 
 import torch  # noqa: F401  (loads torch's HIP runtime first; our .so resolves libamdhip64.so.7 to it)
 
-__all__ = ["lib", "require", "available", "LIB_PATH", "stream_ptr"]
+__all__ = ["lib", "require", "available", "call", "LIB_PATH", "stream_ptr"]
 
 LIB_PATH = os.environ.get("ALINK_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libalink_hip.so")
 _lib: Optional[ctypes.CDLL] = None
@@ -34,20 +34,25 @@ def _load():
     except OSError as e:  # pragma: no cover - depends on box
         _err = f"cannot load {LIB_PATH}: {e}"
         return None
-    c_i64, c_int, c_vp = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
-    L.alink_kmeans_reduce_slabs.argtypes = [c_vp, c_vp, c_int, c_int, c_vp, c_vp]
-    L.alink_kmeans_reduce_slabs.restype = c_int
-    L.alink_kmeans_prep_centroids.argtypes = [c_vp, c_int, c_vp, c_vp, c_vp]
-    L.alink_kmeans_prep_centroids.restype = c_int
-    for name, argtypes in _EXTRA_SIGNATURES.items():
-        if hasattr(L, name):
-            getattr(L, name).argtypes = argtypes
-            getattr(L, name).restype = c_int
+    # build_native.py builds the library from this tree, so every table entry must resolve: a library that lacks
+    # one was built from other sources and is refused as a whole (no per-symbol fall-backs downstream)
+    missing = []
+    for name, argtypes in _SIGNATURES.items():
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            missing.append(name)
+            continue
+        fn.argtypes = argtypes
+        fn.restype = ctypes.c_int
+    if missing:
+        _err = f"{LIB_PATH} is stale, it lacks {', '.join(missing)} (run python build_native.py)"
+        return None
     # every entry point is a ``kernel`` span on the timeline when utils.trace is on (host launch cost + device
     # time from HIP events on the caller's stream); one flag check per call otherwise
     from ..utils import trace
-    for name in ["alink_kmeans_reduce_slabs", "alink_kmeans_prep_centroids"] + list(_EXTRA_SIGNATURES):
-        if hasattr(L, name) and not name.endswith(("_grid", "_pad", "_padded_rank", "_kmax", "_alloc", "_free")):
+    for name in _SIGNATURES:
+        if not name.endswith(("_grid", "_pad", "_padded_rank", "_kmax", "_alloc", "_free")):
             setattr(L, name, trace.traced_call(getattr(L, name), name[len("alink_"):]))
     _lib = L
     return _lib
@@ -55,8 +60,10 @@ def _load():
 
 _c_i64, _c_int, _c_vp, _c_f = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_float
 _c_d = ctypes.c_double
-# signatures of further kernels (registered when present in the library)
-_EXTRA_SIGNATURES = {
+# the C ABI: every exported entry point and its argument types (all return int)
+_SIGNATURES = {
+    "alink_kmeans_prep_centroids": [_c_vp, _c_int, _c_vp, _c_vp, _c_vp],
+    "alink_kmeans_reduce_slabs": [_c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp],
     "alink_tree_gather_rows": [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp],
     "alink_tree_hist_fm": [_c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_int, _c_int, _c_int, _c_vp, _c_int,
                            _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_int],
@@ -68,36 +75,26 @@ _EXTRA_SIGNATURES = {
                                           _c_int],
     "alink_kmeans_v7_grid": [_c_i64, _c_int],
     "alink_kmeans_assign_accum_bf16_v10": [_c_vp, _c_i64, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp,
-                                           _c_int],
-    "alink_kmeans_assign_accum_bf16_v10s": [_c_vp, _c_i64, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp,
-                                            _c_int, _c_vp],
-    "alink_kmeans_assign_accum_bf16_v10d": [_c_vp, _c_i64, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp,
-                                            _c_int, _c_vp, _c_int, _c_d],
+                                           _c_int, _c_vp, _c_vp, _c_int, _c_d],
     "alink_kmeans_v10_grid": [_c_i64, _c_int],
-    "alink_kmeans_reduce_slabs2": [_c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp],
     "alink_tree_predict": [_c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_int,
                            _c_vp, _c_vp, _c_vp, _c_vp],
     "alink_tree_codes": [_c_vp, _c_int, _c_vp, _c_vp, _c_int, _c_i64, _c_i64, _c_int, _c_int, _c_vp, _c_vp],
     "alink_gbdt_rank_stats": [_c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp],
-    "alink_kmeans_seed_ref": [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp],
-    "alink_kmeans_seed_ref2": [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_d, _c_vp, _c_vp, _c_vp, _c_vp],
+    "alink_kmeans_seed_ref": [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_d, _c_vp, _c_vp, _c_vp, _c_vp],
     "alink_kmeans_local_lloyd": [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp,
                                  _c_vp, _c_vp, _c_vp, _c_vp],
     "alink_kmeans_par_pick": [_c_vp, _c_i64, _c_i64, _c_i64, _c_d, _c_vp, _c_i64, _c_vp, _c_vp],
+    "alink_kmeans_cost1_bf16": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp],
     "alink_kmeans_nearest_bf16": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_int,
-                                  _c_int, _c_vp],
-    "alink_kmeans_cost1_bf16": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_int, _c_vp],
-    "alink_kmeans_cost1_bf16_sum": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp],
-    "alink_kmeans_nearest_bf16_rg": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_int,
-                                     _c_int, _c_int, _c_vp, _c_vp],
+                                  _c_int, _c_int, _c_vp, _c_vp],
     "alink_linear_grad_f64": [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_int, _c_d, _c_vp, _c_int, _c_vp,
                               _c_vp],
     "alink_linear_grad_pad": [_c_int],
     "alink_linear_search_f64": [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_int, _c_d, _c_d, _c_int, _c_vp,
                                 _c_int, _c_vp, _c_vp],
-    "alink_kmeans_update": [_c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp],
-    "alink_kmeans_update2": [_c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_d, _c_vp,
-                             ctypes.c_uint64, _c_vp],
+    "alink_kmeans_update": [_c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_d, _c_vp,
+                            ctypes.c_uint64, _c_vp],
     "alink_kmeans_host_stat_alloc": [ctypes.POINTER(_c_vp), ctypes.POINTER(_c_vp)],
     "alink_kmeans_host_stat_free": [_c_vp],
     "alink_kmeans_accum_bf16": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp],
@@ -183,6 +180,13 @@ def require() -> ctypes.CDLL:
     if L is None:
         raise RuntimeError(f"alink_amd HIP kernels unavailable: {_err}")
     return L
+
+
+def call(name: str, *args) -> None:
+    """Call entry point ``name``; a non-zero return code raises."""
+    rc = getattr(require(), name)(*args)
+    if rc != 0:
+        raise RuntimeError(f"{name} failed: {rc}")
 
 
 def torch_fallback_allowed() -> bool:

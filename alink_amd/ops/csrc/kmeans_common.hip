@@ -194,20 +194,15 @@ extern "C" {
 // skip != nullptr (needs host_out): the last block also writes *skip = 1 when some cluster is empty or (prev given)
 // the max shift is < tol (the termination test), else 0 — read by a speculative next-superstep assign launch
 // seq != 0 (needs host_out): host_out[2] = seq is written after the two stats (host completion poll)
-int alink_kmeans_update2(const double* buf, int k, const double* prev, double* C, void* cpad, float* ninit,
-                         unsigned long long* stat, int hyst, unsigned long long* host_out, double tol, unsigned* skip,
-                         unsigned long long seq, void* stream) {
+int alink_kmeans_update(const double* buf, int k, const double* prev, double* C, void* cpad, float* ninit,
+                        unsigned long long* stat, int hyst, unsigned long long* host_out, double tol, unsigned* skip,
+                        unsigned long long seq, void* stream) {
     if (k < 1 || k > 128 || ((skip != nullptr || seq != 0ull) && host_out == nullptr)) return -1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (host_out == nullptr && hipMemsetAsync(stat, 0, 2 * sizeof(unsigned long long), st) != hipSuccess) return -2;
     hipLaunchKernelGGL(kmeans_update_kernel, dim3(128), dim3(128), 0, st, buf, k, prev, C, (__bf16*)cpad, ninit,
                        stat, hyst, host_out, tol, skip, seq);
     return (int)hipGetLastError();
-}
-
-int alink_kmeans_update(const double* buf, int k, const double* prev, double* C, void* cpad, float* ninit,
-                        unsigned long long* stat, int hyst, unsigned long long* host_out, void* stream) {
-    return alink_kmeans_update2(buf, k, prev, C, cpad, ninit, stat, hyst, host_out, 0.0, nullptr, 0ull, stream);
 }
 
 // 32 bytes of mapped, coherent pinned host memory for the update's stats: *host = host address, *dev = the
@@ -222,17 +217,12 @@ int alink_kmeans_host_stat_alloc(void** host, void** dev) {
 int alink_kmeans_host_stat_free(void* host) { return (int)hipHostFree(host); }
 
 // skip (nullable): the update's skip word; when nonzero at run time the reduction returns at once (out untouched)
-int alink_kmeans_reduce_slabs2(const float* slab, const float* slab_cnt, int nslab, int k, double* out,
-                               const void* skip, void* stream) {
+int alink_kmeans_reduce_slabs(const float* slab, const float* slab_cnt, int nslab, int k, double* out,
+                              const void* skip, void* stream) {
     if (k < 1 || k > 128 || nslab < 1) return -1;
     hipLaunchKernelGGL(kmeans_reduce_slabs_kernel, dim3(k, 5), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        slab, slab_cnt, nslab, k, out, (const unsigned*)skip);
     return (int)hipGetLastError();
-}
-
-int alink_kmeans_reduce_slabs(const float* slab, const float* slab_cnt, int nslab, int k, double* out,
-                              void* stream) {
-    return alink_kmeans_reduce_slabs2(slab, slab_cnt, nslab, k, out, nullptr, stream);
 }
 
 int alink_kmeans_prep_centroids(const double* C, int k, void* cpad, float* ninit, void* stream) {

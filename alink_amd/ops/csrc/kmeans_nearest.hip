@@ -806,8 +806,8 @@ extern "C" {
 // variant (rows in flight per lane / load policy; profiles/kmeans_init_r5.txt): 0 = 8, non-temporal loads and
 // stores; 1 = 8, cached (the default: 4.77 ms at 1e8 x 128, 5.5 TB/s); 2 = 16, non-temporal; 3 = 4, non-temporal
 // wsum: nullptr, or [grid * 4] per-wave cost sums (kmeans_cost1_kernel)
-int alink_kmeans_cost1_bf16_sum(const void* X, int64_t N, int D, const void* c, double* cost, double* wsum, int grid,
-                                int variant, void* stream) {
+int alink_kmeans_cost1_bf16(const void* X, int64_t N, int D, const void* c, double* cost, double* wsum, int grid,
+                            int variant, void* stream) {
     if (N <= 0 || grid <= 0) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const __bf16* Xb = reinterpret_cast<const __bf16*>(X);
@@ -821,25 +821,14 @@ int alink_kmeans_cost1_bf16_sum(const void* X, int64_t N, int D, const void* c, 
     }
 }
 
-int alink_kmeans_cost1_bf16(const void* X, int64_t N, int D, const void* c, double* cost, int grid, int variant,
-                            void* stream) {
-    return alink_kmeans_cost1_bf16_sum(X, N, D, c, cost, nullptr, grid, variant, stream);
-}
-
 // reference-rule k-means++ picks over n <= 4096 candidates (kmeans_seed_ref_kernel): D [n][n], w [n], U [k-1];
 // idx0 < 0: the first pick from r0 (the first candidate whose cumulative weight reaches r0 x total)
-int alink_kmeans_seed_ref2(const double* D, const double* w, const double* U, int n, int k, int idx0, double r0,
-                           int64_t* chosen, double* mintot, long long* prof, void* stream) {
+int alink_kmeans_seed_ref(const double* D, const double* w, const double* U, int n, int k, int idx0, double r0,
+                          int64_t* chosen, double* mintot, long long* prof, void* stream) {
     if (n < 1 || n > SEED_NMAX || k < 1 || idx0 >= n) return 1;
     hipLaunchKernelGGL(kmeans_seed_ref_kernel, dim3(1), dim3(SEED_T), 0, reinterpret_cast<hipStream_t>(stream), D, w,
                        U, n, k, idx0, r0, chosen, mintot, prof);
     return hipGetLastError() == hipSuccess ? 0 : 2;
-}
-
-int alink_kmeans_seed_ref(const double* D, const double* w, const double* U, int n, int k, int idx0, int64_t* chosen,
-                          double* mintot, void* stream) {
-    if (idx0 < 0) return 1;
-    return alink_kmeans_seed_ref2(D, w, U, n, k, idx0, 0.0, chosen, mintot, nullptr, stream);
 }
 
 // weighted Lloyd on n <= 4096 fp64 candidates X [n][d], weights w [n], k centroids C [k][d] (in/out; taken from
@@ -876,9 +865,9 @@ int alink_kmeans_par_pick(const double* cost, int64_t n, int64_t first_row, int6
 // iteration (1 or 2; 2 needs D <= 128)
 // counts != nullptr: no per-row output (out_idx / out_d2 unused, merge must be 0); counts[j] (uint64, zeroed by the
 // caller) += rows whose nearest candidate is j — the k-means|| candidate weights of a single-launch candidate set
-int alink_kmeans_nearest_bf16_rg(const void* X, int64_t N, int D, const void* C, const float* chalf, int m, int c0,
-                                 int* out_idx, float* out_d2, int merge, int grid, int rg, void* counts_v,
-                                 void* stream) {
+int alink_kmeans_nearest_bf16(const void* X, int64_t N, int D, const void* C, const float* chalf, int m, int c0,
+                              int* out_idx, float* out_d2, int merge, int grid, int rg, void* counts_v,
+                              void* stream) {
     if (N <= 0 || m <= 0 || m > NB_MAX * 32 || grid <= 0 || rg < 1 || rg > 4 || (rg > 1 && D > 128)) return 1;
     unsigned long long* counts = reinterpret_cast<unsigned long long*>(counts_v);
     if (counts != nullptr && (merge || c0 != 0)) return 1;
@@ -899,11 +888,6 @@ int alink_kmeans_nearest_bf16_rg(const void* X, int64_t N, int D, const void* C,
         case 256: return launch<16, 1>(X, N, C, chalf, m, c0, out_idx, out_d2, merge, grid, st, counts);
         default: return 1;
     }
-}
-
-int alink_kmeans_nearest_bf16(const void* X, int64_t N, int D, const void* C, const float* chalf, int m, int c0,
-                              int* out_idx, float* out_d2, int merge, int grid, void* stream) {
-    return alink_kmeans_nearest_bf16_rg(X, N, D, C, chalf, m, c0, out_idx, out_d2, merge, grid, 1, nullptr, stream);
 }
 
 }  // extern "C"

@@ -71,6 +71,15 @@ def _prepared_is(dev_index, C: torch.Tensor) -> bool:
     return key_matches(_PREPARED.get(dev_index), C)
 
 
+def _prep_operands(dev) -> Tuple[torch.Tensor, torch.Tensor]:
+    """This device's (cpad bf16 [128,128], ninit fp32 [128]) operand buffers of the fused kernels (``_PREP``)."""
+    ops = _PREP.get(dev.index)
+    if ops is None:
+        ops = _PREP[dev.index] = (torch.empty((HIP_KMAX, HIP_D), dtype=torch.bfloat16, device=dev),
+                                  torch.empty((HIP_KMAX,), dtype=torch.float32, device=dev))
+    return ops
+
+
 def prepare_centroids(C: torch.Tensor, device) -> Tuple[torch.Tensor, torch.Tensor]:
     """Padded bf16 centroid block [128,128] and accumulator init -|c|^2/2 (of the bf16-rounded centroids).
     fp64 centroids on the GPU go through one HIP launch into per-device buffers (stream-ordered reuse); when
@@ -79,17 +88,11 @@ def prepare_centroids(C: torch.Tensor, device) -> Tuple[torch.Tensor, torch.Tens
     if C.is_cuda and C.dtype == torch.float64 and C.shape[1] == HIP_D and k <= HIP_KMAX:
         if _prepared_is(C.device.index, C) and C.device.index in _PREP:
             return _PREP[C.device.index]
-        L = _lib.require()
-        key = C.device.index
-        if key not in _PREP:
-            _PREP[key] = (torch.empty((HIP_KMAX, HIP_D), dtype=torch.bfloat16, device=C.device),
-                          torch.empty((HIP_KMAX,), dtype=torch.float32, device=C.device))
-        cpad, ninit = _PREP[key]
+        cpad, ninit = _prep_operands(C.device)
         Cc = C.contiguous()
-        rc = L.alink_kmeans_prep_centroids(Cc.data_ptr(), k, cpad.data_ptr(), ninit.data_ptr(), _lib.stream_ptr(C.device))
-        if rc != 0:
-            raise RuntimeError(f"alink_kmeans_prep_centroids failed: {rc}")
-        _PREPARED[key] = _ckey(C) if Cc is C else None
+        _lib.call("alink_kmeans_prep_centroids", Cc.data_ptr(), k, cpad.data_ptr(), ninit.data_ptr(),
+                  _lib.stream_ptr(C.device))
+        _PREPARED[C.device.index] = _ckey(C) if Cc is C else None
         return cpad, ninit
     cb = C.to(device=device, dtype=torch.bfloat16)
     cpad = torch.zeros((HIP_KMAX, HIP_D), dtype=torch.bfloat16, device=device)
@@ -241,33 +244,21 @@ def _assign_accumulate_hip(X: torch.Tensor, C: torch.Tensor, grid: Optional[int]
         mode |= (V7_VAR << 4) if ver == "v7" else (V10_FLAGS << 4)
     if reverse and ver == "v10":
         mode |= 32
-    skipped = skip is not None and ver == "v10" and V10_POOL <= 0
-    if skipped:
-        rc = L.alink_kmeans_assign_accum_bf16_v10s(
-            X.data_ptr(), n, cpad.data_ptr(), ninit.data_ptr(), k, slab.data_ptr(), slab_cnt.data_ptr(), grid, st,
-            None if assign_out is None else assign_out.data_ptr(), int(mode), skip.data_ptr())
-    elif ver == "v10" and V10_POOL > 0 and (mode & 7) == 0 and hasattr(L, "alink_kmeans_assign_accum_bf16_v10d"):
+    args = [X.data_ptr(), n, cpad.data_ptr(), ninit.data_ptr(), k, slab.data_ptr(), slab_cnt.data_ptr(), grid, st,
+            None if assign_out is None else assign_out.data_ptr(), int(mode)]
+    skip_ptr = skip.data_ptr() if skip is not None and ver == "v10" and V10_POOL <= 0 else None
+    if ver == "v10" and V10_POOL > 0 and (mode & 7) == 0:
         dyn = _DYN.get(dev.index)
         if dyn is None:
             dyn = _DYN[dev.index] = [torch.zeros(2, dtype=torch.int32, device=dev), 0]
-        rc = L.alink_kmeans_assign_accum_bf16_v10d(
-            X.data_ptr(), n, cpad.data_ptr(), ninit.data_ptr(), k, slab.data_ptr(), slab_cnt.data_ptr(), grid, st,
-            None if assign_out is None else assign_out.data_ptr(), int(mode), dyn[0].data_ptr(), dyn[1], V10_POOL)
+        args += [None, dyn[0].data_ptr(), dyn[1], V10_POOL]
         dyn[1] ^= 1
-    else:
-        rc = getattr(L, f"alink_kmeans_assign_accum_bf16_{ver}")(
-            X.data_ptr(), n, cpad.data_ptr(), ninit.data_ptr(), k, slab.data_ptr(), slab_cnt.data_ptr(), grid, st,
-            None if assign_out is None else assign_out.data_ptr(), int(mode))
-    if rc != 0:
-        raise RuntimeError(f"alink_kmeans_assign_accum_bf16_{ver} failed: {rc}")
-    if skipped and hasattr(L, "alink_kmeans_reduce_slabs2"):
-        # the reduction reads the same skip word: a skipped launch costs two empty kernels, not a slab pass
-        rc = L.alink_kmeans_reduce_slabs2(slab.data_ptr(), slab_cnt.data_ptr(), grid, k, out.data_ptr(),
-                                          skip.data_ptr(), st)
-    else:
-        rc = L.alink_kmeans_reduce_slabs(slab.data_ptr(), slab_cnt.data_ptr(), grid, k, out.data_ptr(), st)
-    if rc != 0:
-        raise RuntimeError(f"alink_kmeans_reduce_slabs failed: {rc}")
+    elif ver == "v10":
+        args += [skip_ptr, None, 0, 0.0]        # no counters: the static split
+    _lib.call(f"alink_kmeans_assign_accum_bf16_{ver}", *args)
+    # the reduction reads the same skip word: a skipped launch costs two empty kernels, not a slab pass
+    _lib.call("alink_kmeans_reduce_slabs", slab.data_ptr(), slab_cnt.data_ptr(), grid, k, out.data_ptr(), skip_ptr,
+              st)
     return out
 
 
@@ -361,14 +352,11 @@ def update_centroids_hip(buf: torch.Tensor, prev: Optional[torch.Tensor], deferr
     L = _lib.require()
     dev = buf.device
     k = buf.shape[0]
-    if dev.index not in _PREP:
-        _PREP[dev.index] = (torch.empty((HIP_KMAX, HIP_D), dtype=torch.bfloat16, device=dev),
-                            torch.empty((HIP_KMAX,), dtype=torch.float32, device=dev))
+    cpad, ninit = _prep_operands(dev)
     if dev.index not in _STAT:
         _STAT[dev.index] = _HostStat(L, dev)
     hs = _STAT[dev.index]
     stat = hs.stat
-    cpad, ninit = _PREP[dev.index]
     use_prev = prev is not None and prev.is_cuda and prev.dtype == torch.float64 and tuple(prev.shape) == (k, HIP_D)
     pv = prev.contiguous() if use_prev else None
     C = torch.empty((k, HIP_D), dtype=torch.float64, device=dev)
@@ -380,12 +368,10 @@ def update_centroids_hip(buf: torch.Tensor, prev: Optional[torch.Tensor], deferr
         if skip is None:
             skip = _SKIP[dev.index] = torch.zeros(1, dtype=torch.int32, device=dev)
     seq = hs.next_seq()
-    rc = L.alink_kmeans_update2(buf.data_ptr(), k, None if pv is None else pv.data_ptr(), C.data_ptr(),
-                                cpad.data_ptr(), ninit.data_ptr(), stat.data_ptr(), int(bool(hysteresis)),
-                                hs.dev_ptr, float(skip_tol) if skip is not None else 0.0,
-                                None if skip is None else skip.data_ptr(), seq, _lib.stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"alink_kmeans_update failed: {rc}")
+    _lib.call("alink_kmeans_update", buf.data_ptr(), k, None if pv is None else pv.data_ptr(), C.data_ptr(),
+              cpad.data_ptr(), ninit.data_ptr(), stat.data_ptr(), int(bool(hysteresis)), hs.dev_ptr,
+              float(skip_tol) if skip is not None else 0.0, None if skip is None else skip.data_ptr(), seq,
+              _lib.stream_ptr(dev))
     if hs.dev_ptr is None:
         hs.host.copy_(stat[:2], non_blocking=True)
     ev = None
@@ -420,7 +406,6 @@ def cost1_hip(X: torch.Tensor, c: torch.Tensor, with_sum: bool = False):
     X) -- ``csrc/kmeans_nearest.hip`` kmeans_cost1_kernel, one coalesced streaming pass (the first k-means|| cost).
     ``with_sum``: also the per-wave sums of the costs (fp64 [waves], a fixed order for a given grid), so the
     oversampling threshold's total needs no second pass over the [N] costs: returns (cost, partial sums)."""
-    L = _lib.require()
     if not nearest_supported(X):
         raise ValueError("cost1_hip needs contiguous bf16 [N, D] on GPU with D in (64, 128, 256)")
     n, d = X.shape
@@ -430,11 +415,8 @@ def cost1_hip(X: torch.Tensor, c: torch.Tensor, with_sum: bool = False):
     cost = torch.empty(n, dtype=torch.float64, device=X.device)
     grid = COST1_GRID * _num_cus(X.device)
     wsum = torch.empty(grid * 4, dtype=torch.float64, device=X.device) if with_sum else None
-    rc = L.alink_kmeans_cost1_bf16_sum(X.data_ptr(), n, d, cb.data_ptr(), cost.data_ptr(),
-                                       None if wsum is None else wsum.data_ptr(), grid, COST1_VARIANT,
-                                       _lib.stream_ptr(X.device))
-    if rc != 0:
-        raise RuntimeError(f"alink_kmeans_cost1_bf16 failed: {rc}")
+    _lib.call("alink_kmeans_cost1_bf16", X.data_ptr(), n, d, cb.data_ptr(), cost.data_ptr(),
+              None if wsum is None else wsum.data_ptr(), grid, COST1_VARIANT, _lib.stream_ptr(X.device))
     return (cost, wsum) if with_sum else cost
 
 
@@ -442,7 +424,6 @@ def nearest_counts_hip(X: torch.Tensor, C: torch.Tensor) -> torch.Tensor:
     """int64 [m]: how many rows of X have each centroid as their nearest — ``nearest_hip`` + ``bincount`` in ONE
     pass with no per-row output (per-workgroup LDS counts, integer global adds) when the m <= 256 centroids fit one
     launch; otherwise the two-step form.  Ties and rounding exactly as ``nearest_hip``."""
-    L = _lib.require()
     if not nearest_supported(X):
         raise ValueError("nearest_counts_hip needs contiguous bf16 [N, D] on GPU with D in (64, 128, 256)")
     n, d = X.shape
@@ -454,12 +435,8 @@ def nearest_counts_hip(X: torch.Tensor, C: torch.Tensor) -> torch.Tensor:
         raise ValueError("centroid shape mismatch")
     chalf = (0.5 * (Cb.float() ** 2).sum(1)).contiguous()
     counts = torch.zeros(m, dtype=torch.int64, device=X.device)
-    rg = _rg(d, m)
-    rc = L.alink_kmeans_nearest_bf16_rg(X.data_ptr(), n, d, Cb.data_ptr(), chalf.data_ptr(), m, 0, None, None, 0,
-                                        NEAREST_GRID * _num_cus(X.device), rg, counts.data_ptr(),
-                                        _lib.stream_ptr(X.device))
-    if rc != 0:
-        raise RuntimeError(f"alink_kmeans_nearest_bf16 (counts) failed: {rc}")
+    _lib.call("alink_kmeans_nearest_bf16", X.data_ptr(), n, d, Cb.data_ptr(), chalf.data_ptr(), m, 0, None, None, 0,
+              NEAREST_GRID * _num_cus(X.device), _rg(d, m), counts.data_ptr(), _lib.stream_ptr(X.device))
     return counts
 
 
@@ -501,10 +478,20 @@ GENERAL_CALLS = 0
 _ACC: Dict[Tuple, Tuple[torch.Tensor, torch.Tensor]] = {}
 
 
+def _acc_slabs(dev, nslab: int, k: int, d: int, *tag) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp32 partial-sum scratch (slab [nslab * k * d], slab_cnt [nslab * k]) of the accumulate-by-index kernels:
+    one pair is held at a time (``_ACC`` clears when the key changes)."""
+    key = (dev.index, nslab, k, d, *tag)
+    if key not in _ACC:
+        _ACC.clear()
+        _ACC[key] = (torch.empty(nslab * k * d, dtype=torch.float32, device=dev),
+                     torch.empty(nslab * k, dtype=torch.float32, device=dev))
+    return _ACC[key]
+
+
 def accumulate_by_index_hip(X: torch.Tensor, idx: torch.Tensor, k: int,
                             weights: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[k, d+1] fp64 ``[sum_r w_r x_r | sum_r w_r]`` per index value (``csrc/kmeans_accum.hip``)."""
-    L = _lib.require()
     n, d = X.shape
     dev = X.device
     if idx.dtype != torch.int32 or idx.numel() != n or idx.device != dev:
@@ -515,7 +502,7 @@ def accumulate_by_index_hip(X: torch.Tensor, idx: torch.Tensor, k: int,
         if w.numel() != n:
             raise ValueError("weights length mismatch")
     if X.dtype == torch.float32:
-        return _accumulate_f32(L, X, idx, k, w)
+        return _accumulate_f32(X, idx, k, w)
     if d == HIP_D // 2 and w is None and k <= 256 and X.is_contiguous() and n >= 2:
         # d = 64 on the d = 128 MFMA kernel: view row v = (row 2v | row 2v+1); pass A one-hot by idx[2v] keeps
         # dims 0..63, pass B by idx[2v+1] keeps dims 64..127 — two reads of X at MFMA speed instead of one pass of
@@ -540,52 +527,32 @@ def accumulate_by_index_hip(X: torch.Tensor, idx: torch.Tensor, k: int,
     if d == HIP_D and w is None and k <= 256:
         # MFMA one-hot GEMM fed by idx (csrc/kmeans_accum.hip kmeans_accum_mfma_kernel)
         grid = _num_cus(dev)
-        key = (dev.index, grid, k, d, "mfma")
-        if key not in _ACC:
-            _ACC.clear()
-            _ACC[key] = (torch.empty(grid * k * d, dtype=torch.float32, device=dev),
-                         torch.empty(grid * k, dtype=torch.float32, device=dev))
-        slab, slab_cnt = _ACC[key]
+        slab, slab_cnt = _acc_slabs(dev, grid, k, d, "mfma")
         out = torch.empty((k, d + 1), dtype=torch.float64, device=dev)
-        rc = L.alink_kmeans_accum_mfma_bf16(X.data_ptr(), n, idx.contiguous().data_ptr(), k, grid, slab.data_ptr(),
-                                            slab_cnt.data_ptr(), out.data_ptr(), _lib.stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError(f"alink_kmeans_accum_mfma_bf16 failed: {rc}")
+        _lib.call("alink_kmeans_accum_mfma_bf16", X.data_ptr(), n, idx.contiguous().data_ptr(), k, grid,
+                  slab.data_ptr(), slab_cnt.data_ptr(), out.data_ptr(), _lib.stream_ptr(dev))
         return out
     nchunk = max(1, min(_num_cus(dev), (n + 4095) // 4096))
-    key = (dev.index, nchunk, k, d)
-    if key not in _ACC:
-        _ACC.clear()
-        _ACC[key] = (torch.empty(nchunk * k * d, dtype=torch.float32, device=dev),
-                     torch.empty(nchunk * k, dtype=torch.float32, device=dev))
-    slab, slab_cnt = _ACC[key]
+    slab, slab_cnt = _acc_slabs(dev, nchunk, k, d)
     out = torch.empty((k, d + 1), dtype=torch.float64, device=dev)
-    rc = L.alink_kmeans_accum_bf16(X.data_ptr(), n, d, idx.contiguous().data_ptr(),
-                                   None if w is None else w.data_ptr(), k, nchunk, slab.data_ptr(),
-                                   slab_cnt.data_ptr(), out.data_ptr(), _lib.stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"alink_kmeans_accum_bf16 failed: {rc}")
+    _lib.call("alink_kmeans_accum_bf16", X.data_ptr(), n, d, idx.contiguous().data_ptr(),
+              None if w is None else w.data_ptr(), k, nchunk, slab.data_ptr(), slab_cnt.data_ptr(), out.data_ptr(),
+              _lib.stream_ptr(dev))
     return out
 
 
-def _accumulate_f32(L, X: torch.Tensor, idx: torch.Tensor, k: int, w: Optional[torch.Tensor]) -> torch.Tensor:
+def _accumulate_f32(X: torch.Tensor, idx: torch.Tensor, k: int, w: Optional[torch.Tensor]) -> torch.Tensor:
     n, d = X.shape
     dev = X.device
     if not f32_supported(X, k):
         raise ValueError("fp32 accumulate needs contiguous 16-B aligned fp32 [N, D] (D = 64 or a multiple of 128 "
                          "up to 1024) on the GPU and k within the LDS table limit")
     nchunk = max(1, min(_num_cus(dev), (n + 4095) // 4096))
-    key = (dev.index, nchunk, k, d, "f32")
-    if key not in _ACC:
-        _ACC.clear()
-        _ACC[key] = (torch.empty(nchunk * k * d, dtype=torch.float32, device=dev),
-                     torch.empty(nchunk * k, dtype=torch.float32, device=dev))
-    slab, slab_cnt = _ACC[key]
+    slab, slab_cnt = _acc_slabs(dev, nchunk, k, d, "f32")
     out = torch.empty((k, d + 1), dtype=torch.float64, device=dev)
-    rc = L.alink_kmeans_accum_f32(X.data_ptr(), n, d, idx.contiguous().data_ptr(), None if w is None else w.data_ptr(),
-                                  k, nchunk, slab.data_ptr(), slab_cnt.data_ptr(), out.data_ptr(), _lib.stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"alink_kmeans_accum_f32 failed: {rc}")
+    _lib.call("alink_kmeans_accum_f32", X.data_ptr(), n, d, idx.contiguous().data_ptr(),
+              None if w is None else w.data_ptr(), k, nchunk, slab.data_ptr(), slab_cnt.data_ptr(), out.data_ptr(),
+              _lib.stream_ptr(dev))
     return out
 
 
@@ -723,7 +690,6 @@ def par_pick_hip(cost: torch.Tensor, first_row: int, key: int, thre: float) -> t
     sorted local indices i with ``u(first_row + i) < cost[i] * thre`` — the same picks, bit for bit, as the torch
     expression over ``models/clustering/kmeans._row_uniform`` (splitmix64 of the global row index, ``key`` being
     its signed 64-bit round key), without materialising the [N] uniforms.  One 8-byte read for the pick count."""
-    L = _lib.require()
     dev = cost.device
     n = int(cost.shape[0])
     cost = cost.contiguous()
@@ -731,10 +697,8 @@ def par_pick_hip(cost: torch.Tensor, first_row: int, key: int, thre: float) -> t
     while True:
         out = torch.empty(cap, dtype=torch.int64, device=dev)
         cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-        rc = L.alink_kmeans_par_pick(cost.data_ptr(), n, int(first_row), int(key), float(thre), out.data_ptr(),
-                                     cap, cnt.data_ptr(), _lib.stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError(f"alink_kmeans_par_pick failed: {rc}")
+        _lib.call("alink_kmeans_par_pick", cost.data_ptr(), n, int(first_row), int(key), float(thre), out.data_ptr(),
+                  cap, cnt.data_ptr(), _lib.stream_ptr(dev))
         c = int(cnt.item())
         if c <= cap:
             return torch.sort(out[:c]).values
@@ -747,16 +711,13 @@ def seed_ref_hip(D: torch.Tensor, w: torch.Tensor, U: torch.Tensor, k: int, idx0
     (``csrc/kmeans_nearest.hip`` ``kmeans_seed_ref_kernel``): D [n, n] fp64 plain distances, w [n] weights,
     U [k-1] the picks' uniforms.  ``idx0 < 0``: the first pick too, from the uniform ``r0`` over the sequential
     cumulative weights.  Returns (chosen int64 [k], mintot fp64 [1]) on the device, nothing read back."""
-    L = _lib.require()
     n = int(D.shape[0])
     chosen = torch.empty(k, dtype=torch.int64, device=D.device)
     mintot = torch.full((1,), float("inf"), dtype=torch.float64, device=D.device)
     Dc, wc, Uc = D.contiguous(), w.contiguous(), U.contiguous()
-    rc = L.alink_kmeans_seed_ref2(Dc.data_ptr(), wc.data_ptr(), Uc.data_ptr(), n, int(k), int(idx0), float(r0),
-                                  chosen.data_ptr(), mintot.data_ptr(), None if prof is None else prof.data_ptr(),
-                                  _lib.stream_ptr(D.device))
-    if rc != 0:
-        raise RuntimeError(f"alink_kmeans_seed_ref2 failed: {rc}")
+    _lib.call("alink_kmeans_seed_ref", Dc.data_ptr(), wc.data_ptr(), Uc.data_ptr(), n, int(k), int(idx0), float(r0),
+              chosen.data_ptr(), mintot.data_ptr(), None if prof is None else prof.data_ptr(),
+              _lib.stream_ptr(D.device))
     return chosen, mintot
 
 
@@ -788,7 +749,6 @@ def local_lloyd_hip(X: torch.Tensor, w: torch.Tensor, k: int, C: Optional[torch.
     status fp64 [6] = iterations, changed, empty, non-finite input, mintot, chosen[0], live uint8 [k]), all on the
     device: the caller reads ``status`` once.  ``prof``: int64 [50] receives 100 MHz wall-clock stamps (setup, then
     six phases per iteration for the first 8; tools/kmeans_local_bench.py)."""
-    L = _lib.require()
     n, d = X.shape
     dev = X.device
     Xc = X.contiguous()
@@ -805,12 +765,10 @@ def local_lloyd_hip(X: torch.Tensor, w: torch.Tensor, k: int, C: Optional[torch.
     status = torch.zeros(6, dtype=torch.float64, device=dev)
     live = torch.empty(k, dtype=torch.uint8, device=dev)
     ch = chosen.contiguous() if chosen is not None else None
-    rc = L.alink_kmeans_local_lloyd(Xc.data_ptr(), wc.data_ptr(), n, d, int(k), None if ch is None else ch.data_ptr(),
-                                    C.data_ptr(), assign.data_ptr(), bd.data_ptr(), bi.data_ptr(), int(max_iter),
-                                    None if mintot is None else mintot.data_ptr(), status.data_ptr(), live.data_ptr(),
-                                    None if prof is None else prof.data_ptr(), _lib.stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"alink_kmeans_local_lloyd failed: {rc}")
+    _lib.call("alink_kmeans_local_lloyd", Xc.data_ptr(), wc.data_ptr(), n, d, int(k),
+              None if ch is None else ch.data_ptr(), C.data_ptr(), assign.data_ptr(), bd.data_ptr(), bi.data_ptr(),
+              int(max_iter), None if mintot is None else mintot.data_ptr(), status.data_ptr(), live.data_ptr(),
+              None if prof is None else prof.data_ptr(), _lib.stream_ptr(dev))
     return C, assign, status, live
 
 
@@ -818,7 +776,6 @@ def nearest_hip(X: torch.Tensor, C: torch.Tensor) -> Tuple[torch.Tensor, torch.T
     """(index int32 [N], squared Euclidean distance float32 [N]) of every row's nearest centroid —
     ``csrc/kmeans_nearest.hip``: one MFMA pass over X per 256 centroids (k-means|| seeding, predict).
     Centroids are rounded to bf16 (k-means|| candidates are rows of X, so exactly representable)."""
-    L = _lib.require()
     if not nearest_supported(X):
         raise ValueError("nearest_hip needs contiguous bf16 [N, D] on GPU with D in (64, 128, 256)")
     n, d = X.shape
@@ -833,9 +790,6 @@ def nearest_hip(X: torch.Tensor, C: torch.Tensor) -> Tuple[torch.Tensor, torch.T
     for c0 in range(0, Cb.shape[0], NEAREST_CHUNK):
         m = min(NEAREST_CHUNK, Cb.shape[0] - c0)
         # one centroid block (the first k-means|| cost pass): load-bound, RG = 1 measured 2 % ahead
-        rg = _rg(d, m)
-        rc = L.alink_kmeans_nearest_bf16_rg(X.data_ptr(), n, d, Cb[c0].data_ptr(), chalf[c0].data_ptr(), m, c0,
-                                            idx.data_ptr(), d2.data_ptr(), int(c0 > 0), grid, rg, None, st)
-        if rc != 0:
-            raise RuntimeError(f"alink_kmeans_nearest_bf16 failed: {rc}")
+        _lib.call("alink_kmeans_nearest_bf16", X.data_ptr(), n, d, Cb[c0].data_ptr(), chalf[c0].data_ptr(), m, c0,
+                  idx.data_ptr(), d2.data_ptr(), int(c0 > 0), grid, _rg(d, m), None, st)
     return idx, d2

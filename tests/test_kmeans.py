@@ -275,3 +275,63 @@ def test_kmeans_predict_detail_packed_with_nulls():
     for r in rows[:-1]:
         p = np.array([float(x) for x in r[2].split(" ")])
         assert r[2] == VectorUtil.toString(DenseVector(p)) and abs(p.sum() - 1) < 1e-12
+
+
+def _numpy_lloyd(X, C, dist, tol, max_iter):
+    """Plain Lloyd with the update rule of KMeansUpdateCentroids: empty clusters are dropped, the shift is compared
+    only when the previous and the new centroids have the same shape, COSINE renormalises the rows."""
+    for _ in range(max_iter):
+        idx = (X @ C.T - 0.5 * (C * C).sum(1)).argmax(1)
+        cnt = np.bincount(idx, minlength=len(C)).astype(np.float64)
+        S = np.zeros_like(C)
+        np.add.at(S, idx, X)
+        keep = cnt > 0
+        new, cnt = S[keep] / cnt[keep, None], cnt[keep]
+        if dist == "COSINE":
+            new = new / np.linalg.norm(new, axis=1, keepdims=True)
+        done = False
+        if new.shape == C.shape:
+            shift = (1.0 - (new * C).sum(1)) if dist == "COSINE" else np.sqrt(((new - C) ** 2).sum(1))
+            done = shift.max() < tol
+        C = new
+        if done:
+            break
+    return C, cnt
+
+
+@pytest.mark.parametrize("dist,tol", [("EUCLIDEAN", 1e-6), ("COSINE", 1e-9)])
+def test_generic_update_compacts_empty_cluster(dist, tol):
+    """The generic torch update (fp64 rows on the CPU) drops a cluster that no row joins: k shrinks to 3, the
+    weights still cover every row, and the centroids equal a numpy Lloyd with the same rule.  Tolerance: the fp64
+    sum of 200 O(1) terms carries about 4e-14 of rounding, so 1e-12 absolute."""
+    import torch
+    from alink_amd.models.clustering.kmeans import train_kmeans
+    env = useLocalEnv(1)
+    rng = np.random.default_rng(7)
+    centres = rng.standard_normal((4, 4)) * 5
+    if dist == "COSINE":
+        centres = np.abs(centres) + 0.1
+    X = centres[rng.integers(0, 4, 200)] + 0.1 * rng.standard_normal((200, 4))
+    init = centres + 0.05 * rng.standard_normal((4, 4))
+    if dist == "COSINE":
+        X = np.abs(X) + 1e-3                                        # positive orthant
+        init = np.abs(init)
+        init /= np.linalg.norm(init, axis=1, keepdims=True)
+        init[1] = -init[0]                                          # farthest from every row
+        Xn = X / np.linalg.norm(X, axis=1, keepdims=True)           # train_kmeans normalises the rows
+    else:
+        init[1] = 1e4                                               # no row joins it
+        Xn = X
+    _, q = train_kmeans(torch.from_numpy(X), 4, 20, tol, dist, "RANDOM", 2, "v", env,
+                        init_centroids=torch.from_numpy(init))
+    ctx = q.final_contexts[0]
+    assert ctx.getObj("k") == 3
+    w = ctx.getObj("lastWeights").numpy()
+    assert w.sum() == 200
+    c1, c2 = ctx.getObj("centroid1"), ctx.getObj("centroid2")
+    got = (c1 if c1[0] > c2[0] else c2)[1][:3].numpy()
+    want, cnt = _numpy_lloyd(Xn, init, dist, tol, 20)
+    assert want.shape == (3, 4) and np.array_equal(cnt, w)
+    err = np.abs(got - want).max()
+    print(f"{dist}: {len(q.stats)} supersteps, max |centroid - numpy| = {err:.3e}")
+    assert err <= 1e-12

@@ -376,8 +376,8 @@ def test_update_convergence_word_and_skipped_assign():
     L = K._lib.require()
     key = next(iter(K._BUF))
     s, sc = K._BUF[key]
-    assert L.alink_kmeans_reduce_slabs2(s.data_ptr(), sc.data_ptr(), key[1], 60, poison.data_ptr(),
-                                        read.skip.data_ptr(), K._lib.stream_ptr(poison.device)) == 0
+    assert L.alink_kmeans_reduce_slabs(s.data_ptr(), sc.data_ptr(), key[1], 60, poison.data_ptr(),
+                                       read.skip.data_ptr(), K._lib.stream_ptr(poison.device)) == 0
     torch.cuda.synchronize()
     assert bool((poison == 7.0).all()) and out.shape == (60, 129)
 
