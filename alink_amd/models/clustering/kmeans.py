@@ -23,6 +23,11 @@ MI355X path: rows stay on the GPU; the assign/accumulate step is the fused HIP k
 (``ops/csrc/kmeans_v10.hip`` for bf16 rows with d = 128, ``kmeans_accum.hip`` for other bf16 shapes, see
 ``ops/kmeans.py``), the [k, d+1] all-reduce is the one-shot xGMI kernel (``ops/csrc/allreduce.hip``) or RCCL,
 and the update/criterion is one fused HIP kernel (``kmeans_common.hip``) — no per-sample host work.
+
+Sparse vector columns (a ``SparseBlock``, sparse vectors or sparse vector strings) wider than the dense kernels
+cover train and predict as CSR rows (``ops/kmeans_sparse.py``, ``csrc/kmeans_sparse.hip``): the reference clusters
+``SparseVector``s the same way (``KMeansUtil.updateSumMatrix``, ``KMeansUtil.java:76-83``).  EUCLIDEAN and COSINE;
+only candidate centroid rows are ever densified.
 """
 from __future__ import annotations
 
@@ -44,7 +49,7 @@ from ...params import get_enum, param
 from ...parallel import comm
 from ...parallel.comqueue import (AllReduce, CompareCriterionFunction, CompleteResultFunction, ComputeFunction,
                                   IterativeComQueue)
-from ...ops import _lib, kmeans as kops
+from ...ops import _lib, kmeans as kops, kmeans_sparse as ksp
 
 __all__ = ["ClusterSummary", "KMeansTrainModelData", "KMeansModelDataConverter", "KMeansPredictModelData",
            "KMeansModelMapper", "train_kmeans", "kmeans_init", "pairwise_distance"]
@@ -152,6 +157,40 @@ def _normalize_rows(X: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------------
+# sparse rows (a CSR ``FeatureMatrix``, ``ops/kmeans_sparse.py``): never densified as a whole
+# ---------------------------------------------------------------------------------------------------
+def _is_sparse(X) -> bool:
+    return not isinstance(X, torch.Tensor)
+
+
+def _nrows(X) -> int:
+    return int(X.nrows) if _is_sparse(X) else int(X.shape[0])
+
+
+def _sparse_view(fm, ncols: int, val: Optional[torch.Tensor] = None):
+    """The same CSR arrays as ``fm`` (or other values) under ``ncols`` columns, as a new FeatureMatrix."""
+    from ..common.features import FeatureMatrix
+    return FeatureMatrix(crow=fm.crow, col=fm.col, val=fm.val if val is None else val, ncols=int(ncols))
+
+
+def _normalize_sparse(fm, d: int):
+    """COSINE row normalisation of CSR rows: ``val`` scaled by the row norm over the columns inside [0, d); zero
+    rows stay as they are, as ``_normalize_rows`` leaves them."""
+    if fm.nrows == 0 or fm.val.numel() == 0:
+        return _sparse_view(fm, d)
+    nrm = ksp.row_sqnorm(fm, d).sqrt_()
+    nrm = torch.where(nrm > 0, nrm, torch.ones_like(nrm))
+    return _sparse_view(fm, d, fm.val / nrm[fm.row_ids()])
+
+
+def _rows_dense(X, idx: torch.Tensor) -> torch.Tensor:
+    """The few rows ``idx`` as a dense fp64 block (candidate centroids)."""
+    if _is_sparse(X):
+        return ksp.take_dense(X, idx)
+    return X[idx].to(torch.float64)
+
+
+# ---------------------------------------------------------------------------------------------------
 # initialisation
 # ---------------------------------------------------------------------------------------------------
 def _seed_cost(d: torch.Tensor, dist_type: str) -> torch.Tensor:
@@ -159,10 +198,15 @@ def _seed_cost(d: torch.Tensor, dist_type: str) -> torch.Tensor:
 
 
 def _hip_nearest_ok(X: torch.Tensor, dist_type: str) -> bool:
+    if _is_sparse(X):
+        return False
     return dist_type.upper() == "EUCLIDEAN" and kops.nearest_supported(X) and _lib.available()
 
 
 def _min_dist_to(X: torch.Tensor, C: torch.Tensor, dist_type: str, chunk=1 << 20) -> torch.Tensor:
+    if _is_sparse(X):
+        dist = ksp.nearest(X, C, dist_type)[1]
+        return dist.sqrt_() if dist_type.upper() == "EUCLIDEAN" else dist
     if _hip_nearest_ok(X, dist_type):
         if C.shape[0] == 1:      # the first k-means|| cost: one streaming pass, fp64 distances straight out
             return kops.cost1_hip(X, C[0])
@@ -176,6 +220,8 @@ def _min_dist_to(X: torch.Tensor, C: torch.Tensor, dist_type: str, chunk=1 << 20
 
 
 def _nearest(X: torch.Tensor, C: torch.Tensor, dist_type: str, chunk=1 << 20) -> torch.Tensor:
+    if _is_sparse(X):
+        return ksp.nearest(X, C, dist_type)[0]
     if _hip_nearest_ok(X, dist_type):
         return kops.nearest_hip(X, C)[0].to(torch.int64)
     out = []
@@ -219,13 +265,17 @@ def _fetch_global_rows(X: torch.Tensor, global_idx: List[int], counts: List[int]
     it owns into a zero [m, d] fp64 block and one SUM all-reduce (RCCL on GPU) assembles it — no pickling."""
     rank = comm.get_rank()
     offs = np.concatenate([[0], np.cumsum(counts)])
-    d = max(1, int(X.shape[1])) if X.dim() == 2 else 1
+    if _is_sparse(X):
+        d = max(1, int(X.ncols))
+    else:
+        d = max(1, int(X.shape[1])) if X.dim() == 2 else 1
     out = torch.zeros((len(global_idx), d), dtype=torch.float64, device=X.device)
     mine = [(j, g - offs[rank]) for j, g in enumerate(global_idx) if offs[rank] <= g < offs[rank + 1]]
     if mine:
         dst = torch.as_tensor([j for j, _ in mine], dtype=torch.long, device=X.device)
         src = torch.as_tensor([int(i) for _, i in mine], dtype=torch.long, device=X.device)
-        out.index_copy_(0, dst, X.index_select(0, src).to(torch.float64))
+        out.index_copy_(0, dst, _rows_dense(X, src) if _is_sparse(X) else
+                        X.index_select(0, src).to(torch.float64))
     comm.all_reduce(out)
     return out
 
@@ -387,7 +437,7 @@ def _local_kmeans(samples: torch.Tensor, weights: torch.Tensor, k: int, dist_typ
 def kmeans_init(X: torch.Tensor, k: int, init_mode: str, init_steps: int, dist_type: str,
                 seed: int = 0) -> torch.Tensor:
     """Initial centroids [k', d] float64 (identical on every rank)."""
-    counts = _global_count(X.shape[0])
+    counts = _global_count(_nrows(X))
     n = int(sum(counts))
     if n == 0:
         raise ValueError("The train dataset is empty!")
@@ -414,9 +464,9 @@ def kmeans_init(X: torch.Tensor, k: int, init_mode: str, init_steps: int, dist_t
         if cost.is_cuda and _lib.available():
             pick = kops.par_pick_hip(cost, first_row, _round_key(seed, rnd), thre)
         else:
-            u = _row_uniform(first_row, X.shape[0], seed, rnd, X.device)
+            u = _row_uniform(first_row, _nrows(X), seed, rnd, X.device)
             pick = torch.nonzero(u < cost * thre).reshape(-1)
-        new = comm.all_gather_varlen(X[pick].to(torch.float64))   # rank order == global row order
+        new = comm.all_gather_varlen(_rows_dense(X, pick))   # rank order == global row order
         if new.shape[0] == 0:
             continue
         centers = torch.cat([centers, new])
@@ -426,6 +476,8 @@ def kmeans_init(X: torch.Tensor, k: int, init_mode: str, init_steps: int, dist_t
         return centers
     if _hip_nearest_ok(X, dist_type):
         w = kops.nearest_counts_hip(X, centers).to(torch.float64)      # one pass, no per-row output
+    elif _is_sparse(X):
+        w = ksp.nearest_counts(X, centers, dist_type).to(torch.float64)
     else:
         w = torch.bincount(_nearest(X, centers, dist_type), minlength=centers.shape[0]).to(torch.float64)
     comm.all_reduce(w)
@@ -445,6 +497,9 @@ class KMeansPreallocateCentroid(ComputeFunction):
 
 
 class KMeansAssignCluster(ComputeFunction):
+    def __init__(self, dist_type: str = "EUCLIDEAN"):
+        self.dist_type = dist_type      # read by the sparse path alone (the dense kernels score by |x - c|^2)
+
     def calc(self, ctx):
         cur = ctx.getObj(CENTROID1) if ctx.getStepNo() % 2 == 0 else ctx.getObj(CENTROID2)
         k = ctx.getObj(K)
@@ -455,8 +510,10 @@ class KMeansAssignCluster(ComputeFunction):
         if spec is not None and spec[0][0] == ctx.getStepNo() and kops.key_matches(spec[0][1], C):
             ctx.putObj(CENTROID_ALL_REDUCE, spec[1])    # launched by the previous superstep's update
             return
-        if X is None or X.shape[0] == 0:
+        if X is None or _nrows(X) == 0:
             buf = torch.zeros((k, C.shape[1] + 1), dtype=torch.float64, device=C.device)
+        elif _is_sparse(X):
+            buf = ksp.assign_accumulate(X, C, self.dist_type)
         else:
             buf = kops.assign_accumulate(X, C, reverse=kops.serpentine_reverse(ctx.getStepNo()))
         ctx.putObj(CENTROID_ALL_REDUCE, buf)
@@ -494,7 +551,10 @@ class KMeansUpdateCentroids(ComputeFunction):
         old = ctx.getObj(CENTROID1) if ctx.getStepNo() % 2 == 0 else ctx.getObj(CENTROID2)
         buf = ctx.getObj(CENTROID_ALL_REDUCE)
         prev = old[1] if old is not None and old[1] is not None else None
-        if self.dist_type == "EUCLIDEAN" and kops.update_supported(buf) and \
+        X = ctx.getObj(TRAIN_DATA)
+        # sparse rows never take the fused update: it queues the dense assign kernel for the next superstep
+        dense_rows = X is None or not _is_sparse(X)
+        if self.dist_type == "EUCLIDEAN" and dense_rows and kops.update_supported(buf) and \
                 (_lib_ok() or not kops._lib.torch_fallback_allowed()):
             C, shift, has_empty = self._fused_update(ctx, buf, prev)
             weights = buf[:, -1]
@@ -638,6 +698,11 @@ def train_kmeans(X: torch.Tensor, k: int, max_iter: int, tol: float, dist_type: 
     """Run the KMeans BSP queue on this rank's rows ``X`` ([n, d] on the env device); returns
     (model rows, queue)."""
     dist_type = dist_type.upper()
+    if _is_sparse(X) and not X.is_sparse:
+        X = X.dense
+    if _is_sparse(X):
+        return _train_kmeans_sparse(X, k, max_iter, tol, dist_type, init_mode, init_steps, vector_col, env,
+                                    init_centroids, on_step, seed, sync_steps)
     # opt-in device precision for fp64 feature matrices (VectorAssembler output): ALINK_KMEANS_INPUT=fp32 runs the
     # fp32 GEMM-assign + HIP accumulate path, =bf16 the fused bf16 MFMA kernels (a one-time cast of this rank's
     # rows; profiles/kmeans_fp32_r4.txt records the centroid deltas against fp64)
@@ -651,15 +716,22 @@ def train_kmeans(X: torch.Tensor, k: int, max_iter: int, tol: float, dist_type: 
     vector_size = int(comm.all_reduce(vs, "max").item())
     init = init_centroids if init_centroids is not None else kmeans_init(X, k, init_mode, init_steps, dist_type,
                                                                          seed=seed)
+    return _run_kmeans_queue(X, init, vector_size, k, max_iter, tol, dist_type, vector_col, env, lat_col, lon_col,
+                             on_step, sync_steps)
+
+
+def _run_kmeans_queue(X, init, vector_size, k, max_iter, tol, dist_type, vector_col, env, lat_col, lon_col, on_step,
+                      sync_steps):
+    """The Lloyd BSP queue over this rank's rows ``X`` (a tensor, or a sparse FeatureMatrix) from ``init``."""
     init = init.to(device=X.device, dtype=torch.float64)
     q = (IterativeComQueue()
          .setMLEnvironment(env)
          .setJobName("KMeans")
-         .setRowsPerStep(int(X.shape[0]))
+         .setRowsPerStep(_nrows(X))
          .initWithPartitionedData(TRAIN_DATA, X)
          .initWithBroadcastData(INIT_CENTROID, init)
          .add(KMeansPreallocateCentroid())
-         .add(KMeansAssignCluster())
+         .add(KMeansAssignCluster(dist_type))
          .add(AllReduce(CENTROID_ALL_REDUCE))
          .add(KMeansUpdateCentroids(dist_type, max_iter, sync_steps, tol=tol))
          .setCompareCriterionOfNode0(KMeansIterTermination(dist_type, tol), replicated=True)
@@ -671,6 +743,24 @@ def train_kmeans(X: torch.Tensor, k: int, max_iter: int, tol: float, dist_type: 
         q.addStepCallback(on_step)
     rows = q.exec()
     return rows, q
+
+
+def _train_kmeans_sparse(fm, k, max_iter, tol, dist_type, init_mode, init_steps, vector_col, env, init_centroids,
+                         on_step, seed, sync_steps):
+    """``train_kmeans`` for CSR rows: the same queue, with the assignment, the sums and the k-means|| passes on
+    the sparse kernels (``ops/kmeans_sparse.py``).  Only candidate rows are ever densified."""
+    if dist_type not in ("EUCLIDEAN", "COSINE"):
+        raise ValueError(f"sparse KMeans supports EUCLIDEAN and COSINE, not {dist_type}")
+    vs = torch.tensor([float(fm.ncols) if fm.nrows else 0.0], dtype=torch.float64)
+    vector_size = int(comm.all_reduce(vs, "max").item())
+    if fm.val.dtype != torch.float64:
+        fm = _sparse_view(fm, fm.ncols, fm.val.to(torch.float64))
+    # every rank works in the global vector size (an empty partition knows no size of its own)
+    X = _normalize_sparse(fm, vector_size) if dist_type == "COSINE" else _sparse_view(fm, vector_size)
+    init = init_centroids if init_centroids is not None else kmeans_init(X, k, init_mode, init_steps, dist_type,
+                                                                         seed=seed)
+    return _run_kmeans_queue(X, init, vector_size, k, max_iter, tol, dist_type, vector_col, env, None, None, on_step,
+                             sync_steps)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -744,7 +834,78 @@ class KMeansModelMapper(ModelMapper):
         lon = mt.col(m.longitudeColName).to_list()
         return torch.tensor(np.stack([np.asarray(lat, float), np.asarray(lon, float)], 1)), None
 
+    def _sparse_input(self, mt: MTable):
+        """(sparse FeatureMatrix under the model's vector size, null flags or None) when the vector column is
+        sparse and the sparse path is selected (``ops/kmeans_sparse.sparse_selected``), else None."""
+        m = self.model
+        dt = m.distanceType.upper()
+        if m.vectorColName is None or dt not in ("EUCLIDEAN", "COSINE") or self.C.dim() != 2 or self.C.shape[0] < 1:
+            return None
+        d = int(self.C.shape[1])
+        if os.environ.get("ALINK_KMEANS_SPARSE", "") == "0" or d < 1:
+            return None
+        c = mt.col(m.vectorColName)
+        v = c.values
+        from ...common.linalg import SparseVector
+        from ...common.linalg.block import SparseBlock
+        from ..common.features import FeatureMatrix, _vectors_to_matrix
+        if isinstance(v, SparseBlock):
+            if not ksp.sparse_selected(True, d):
+                return None
+            nulls = c.nulls.cpu().tolist() if c.nulls is not None else None
+            return FeatureMatrix(crow=v.crow, col=v.col, val=v.val, ncols=d), nulls
+        if isinstance(v, torch.Tensor):
+            return None
+        vals = c.to_list()
+        first = next((x for x in vals if x is not None), None)
+        if not (isinstance(first, SparseVector) or (isinstance(first, str) and ("$" in first or ":" in first))):
+            return None
+        if not ksp.sparse_selected(True, d):
+            return None
+        fm = _vectors_to_matrix(vals, torch.float64, torch.device("cpu"), d)
+        if not fm.is_sparse:
+            return None
+        nulls = [x is None for x in vals]
+        return _sparse_view(fm, d), (nulls if any(nulls) else None)
+
+    def _map_sparse(self, fm):
+        """(ids index, best distance, all distances or None) of CSR rows through ``ops/kmeans_sparse.nearest``."""
+        dt = self.model.distanceType.upper()
+        d = int(self.C.shape[1])
+        if dt == "COSINE":
+            fm = _normalize_sparse(fm, d)
+        C = self.C.to(fm.device)
+        idx, best = ksp.nearest(fm, C, dt)
+        if dt == "EUCLIDEAN":
+            best = best.sqrt()
+        dist_all = None
+        if self.detail_col:
+            # every distance, in row chunks of the CSR product (the [n, k] result is the only dense block)
+            col, val = ksp._clipped(fm, d)
+            safe = _sparse_view(fm, d, val)
+            safe.col = col
+            Ct = C.t().contiguous()
+            cn = (C * C).sum(1)[None, :]
+            xn = ksp.row_sqnorm(fm, d)
+            parts = []
+            for s in range(0, fm.nrows, 1 << 16):
+                dot = safe[s:s + (1 << 16)].mm(Ct)
+                parts.append(1.0 - dot if dt == "COSINE" else
+                             torch.sqrt((xn[s:s + (1 << 16), None] + cn - 2.0 * dot).abs()))
+            dist_all = torch.cat(parts) if parts else torch.zeros((0, C.shape[0]), dtype=torch.float64,
+                                                                  device=fm.device)
+        return idx, best, dist_all
+
     def _map_columns(self, mt: MTable):
+        sp = self._sparse_input(mt)
+        if sp is not None:
+            nulls = sp[1]
+            idx, best, dist_all = self._map_sparse(sp[0])
+        else:
+            idx, best, dist_all, nulls = self._map_dense(mt)
+        return self._outputs(idx, best, dist_all, nulls)
+
+    def _map_dense(self, mt: MTable):
         X, nulls = self._input_block(mt)
         dev = X.device
         dt = self.model.distanceType.upper()
@@ -763,6 +924,9 @@ class KMeansModelMapper(ModelMapper):
             C = self.C.to(Xf.device)
             dist_all = pairwise_distance(Xf, C, dt)
             best, idx = dist_all.min(1)
+        return idx, best, dist_all, nulls
+
+    def _outputs(self, idx, best, dist_all, nulls):
         ids = torch.as_tensor(self.model.ids, device=idx.device)[idx]
         outs = [Column(ids.to(torch.int64).cpu())]
         if nulls is not None and any(nulls):

@@ -32,6 +32,44 @@ def vector_tensor(mt: MTable, col: str, device) -> torch.Tensor:
     return blk.to(device)
 
 
+def sparse_vector_matrix(mt: MTable, col: str, device, dist_type: str):
+    """This rank's rows of a SPARSE vector column as a CSR ``FeatureMatrix`` when KMeans takes its sparse path
+    (``ops/kmeans_sparse.sparse_selected``: the column is a ``SparseBlock`` or holds sparse vectors, and the global
+    vector size exceeds what the dense kernels cover; ``ALINK_KMEANS_SPARSE`` = 1 / 0 forces / disables it), else
+    None.  Every rank takes the same decision: a rank without rows follows the others."""
+    import os
+    from ...common.linalg import SparseBlock, SparseVector
+    from ...models.common.features import extract_features
+    from ...ops.kmeans_sparse import sparse_selected
+    from ...parallel import comm
+    if os.environ.get("ALINK_KMEANS_SPARSE", "") == "0" or dist_type.upper() not in ("EUCLIDEAN", "COSINE"):
+        return None
+    v = mt.col(col).values
+    if isinstance(v, torch.Tensor):     # dense block: as in vector_tensor, no collective on this path
+        return None
+    if isinstance(v, SparseBlock):
+        kind = 1
+    else:
+        first = next((x for x in v if x is not None), None)
+        if first is None:
+            kind = -1                   # no rows here: undecided
+        else:
+            kind = int(isinstance(first, SparseVector) or (isinstance(first, str) and ("$" in first or ":" in first)))
+    kinds = comm.all_gather_object(kind)
+    if 0 in kinds or 1 not in kinds:
+        return None
+    fm = extract_features(mt, None, col, device)
+    flags = comm.all_gather_object((int(fm.ncols), bool(fm.is_sparse) or fm.nrows == 0))
+    if not all(f[1] for f in flags) or not sparse_selected(True, max(f[0] for f in flags)):
+        return None
+    if not fm.is_sparse:                # a rank without rows: an empty CSR partition
+        from ...models.common.features import FeatureMatrix
+        z = torch.zeros(0, dtype=torch.int64, device=device)
+        fm = FeatureMatrix(crow=torch.zeros(1, dtype=torch.int64, device=device), col=z,
+                           val=torch.zeros(0, dtype=torch.float64, device=device), ncols=0)
+    return fm
+
+
 class KMeansTrainBatchOp(BatchOperator):
     """k-means on the BSP engine (see ``models/clustering/kmeans.py``)."""
     EXTRA_PARAMS = [ParamInfo("randomSeed", int, "seed of the k-means|| / random initialisation", default=0)]
@@ -40,8 +78,10 @@ class KMeansTrainBatchOp(BatchOperator):
         inp = self.checkAndGetFirst(inputs)
         mt = inp.getOutputTable()
         env = self.env
-        X = vector_tensor(mt, self.getVectorCol(), env.device)
         dt = str(self.getDistanceType().name if hasattr(self.getDistanceType(), "name") else self.getDistanceType())
+        X = sparse_vector_matrix(mt, self.getVectorCol(), env.device, dt)
+        if X is None:
+            X = vector_tensor(mt, self.getVectorCol(), env.device)
         im = self.getInitMode()
         im = im.name if hasattr(im, "name") else str(im)
         rows, q = train_kmeans(X, self.getK(), self.getMaxIter(), self.getEpsilon(), dt, im, self.getInitSteps(),

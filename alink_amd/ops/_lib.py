@@ -164,6 +164,10 @@ _SIGNATURES = {
     "alink_bias_sigmoid_f64": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp],
     "alink_sigmoid_bwd_f64": [_c_vp, _c_vp, _c_i64, _c_vp],
     "alink_als_gram_f32": [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_int, _c_f, _c_vp, _c_vp, _c_vp],
+    "alink_kmeans_sparse_nearest": [_c_vp, _c_vp, _c_int, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_int, _c_d, _c_int,
+                                    _c_vp, _c_vp, _c_vp, _c_int, _c_vp],
+    "alink_kmeans_sparse_accum": [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp,
+                                  _c_int, _c_vp, _c_vp, _c_int, _c_vp],
 }
 
 

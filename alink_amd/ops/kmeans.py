@@ -17,6 +17,9 @@ all-reduce.
   fp32 rows (``csrc/kmeans_accum.hip`` ``alink_kmeans_accum_f32``: fp64 LDS table, fixed-order fp64 reduction).
   fp64 feature matrices (VectorAssembler output) reach it through ``ALINK_KMEANS_INPUT=fp32`` (a one-time cast,
   see ``models/clustering/kmeans.train_kmeans``; ``bf16`` selects the fused bf16 kernels instead).
+* sparse rows (a CSR ``FeatureMatrix``) do not come through this module: ``ops/kmeans_sparse.py`` assigns and sums
+  them in fp64 without densifying (``csrc/kmeans_sparse.hip``; selected by ``models/clustering/kmeans.py`` and the
+  operators for sparse vector columns wider than the dense kernels cover).
 * anything else: chunked PyTorch path (fp64 on CPU; on GPU fp32 GEMM of the same bf16-rounded centroids).
 """
 from __future__ import annotations
