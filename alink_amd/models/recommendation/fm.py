@@ -9,8 +9,10 @@ model averaging ``UpdateGlobalModel`` :262-297, loss / AUC / accuracy :154-257, 
 
 MI355X-first: the reference visits ``batchSize`` randomly drawn samples one at a time per superstep.  Here the
 drawn samples are processed in micro-batches on the rank's device — ``X V`` / ``X^2 V^2`` as one sparse
-(CSR gather + segment-sum) or dense GEMM, the per-occurrence gradients scattered with ``index_add_`` into the
-gradient and squared-gradient accumulators, then one AdaGrad step for the touched coordinates.  The
+(CSR gather + segment-sum) or dense GEMM, the per-occurrence gradients summed per coordinate into the gradient
+and squared-gradient accumulators in a fixed order (a reduction over the batch axis for dense rows, the HIP
+coordinate kernel or sorted segment sums for sparse rows on the GPU, a sequential ``index_add_`` on the CPU: two
+trainings of one job give the same bits), then one AdaGrad step for the touched coordinates.  The
 superstep ends like the reference's: factors, linear items and AdaGrad state weighted by per-feature usage
 are summed in ONE all-reduce and divided by the usage totals.
 """
@@ -161,6 +163,65 @@ def _order_labels(labels: List[Any]) -> List[Any]:
     return [b, a] if java_str(b) > java_str(a) else [a, b]
 
 
+def _coord_sums_dense(X, g, vx, swb, w, V, lam, dim, use, sg_V, sg_w):
+    """Per-coordinate sums of one DENSE micro-batch X [m, vec]: every row touches every coordinate, so the sums
+    over the occurrences of a coordinate are plain reductions over the batch axis -- no scatter, hence no atomics
+    and one fixed order on the GPU.  Adds the usage weights to ``use`` and the squared gradients to ``sg_V`` /
+    ``sg_w`` in place; returns the gradient sums (G [vec, k] or None, Gl [vec] or None)."""
+    use += swb.sum()
+    G = Gl = None
+    gx = g[:, None] * X                                                   # [m, vec]
+    if dim[2] > 0:
+        gv = gx[:, :, None] * (vx[:, None, :] - X[:, :, None] * V[None]) + lam[2] * V[None]     # [m, vec, k]
+        G = gv.sum(0)
+        sg_V += (gv * gv).sum(0)
+    if dim[1] > 0:
+        gl = gx + lam[1] * w[None]
+        Gl = gl.sum(0)
+        sg_w += (gl * gl).sum(0)
+    return G, Gl
+
+
+def _segment_sum(src: torch.Tensor, order: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
+    """Sum of the rows of ``src`` per column segment, rows taken in ``order`` (a stable sort by column): every
+    segment is added up front to back by one thread, the same order on every run."""
+    return torch.segment_reduce(src[order].contiguous(), "sum", lengths=lengths, axis=0, unsafe=True)
+
+
+def _coord_sums_scatter(rows, cols, vals, g, vx, swb, w, V, lam, dim, use, sg_V, sg_w):
+    """The same sums from per-entry (row, column, value) triples of a sparse micro-batch that the coordinate kernel
+    does not take (no factors, or more than 64).  On the CPU ``index_add_`` runs sequentially in entry order.  On
+    the GPU it would add with atomics in no fixed order, so there the entries are sorted by column (stable) and
+    each column's segment is summed in that order."""
+    vec_size = use.shape[0]
+    cols = cols.to(torch.int64)
+    gr = g[rows]
+    on_gpu = vals.is_cuda
+    if on_gpu:
+        order = torch.argsort(cols, stable=True)
+        lengths = torch.bincount(cols, minlength=vec_size)
+
+        def add(dst, src):
+            dst += _segment_sum(src, order, lengths)
+    else:
+        def add(dst, src):
+            dst.index_add_(0, cols, src)
+    add(use, swb[rows])
+    G = Gl = None
+    if dim[2] > 0:
+        Vc = V[cols]
+        gv = (gr * vals)[:, None] * (vx[rows] - vals[:, None] * Vc) + lam[2] * Vc
+        G = torch.zeros_like(V)
+        add(G, gv)
+        add(sg_V, gv * gv)
+    if dim[1] > 0:
+        gl = gr * vals + lam[1] * w[cols]
+        Gl = torch.zeros_like(w)
+        add(Gl, gl)
+        add(sg_w, gl * gl)
+    return G, Gl
+
+
 def train_fm(mt: MTable, p: Params, task: str, env, micro_batch: int = 512):
     """Returns (FmModelData, label type, train info)."""
     dev = env.device
@@ -228,23 +289,13 @@ def train_fm(mt: MTable, p: Params, task: str, env, micro_batch: int = 512):
                                          sg_w if dim[1] > 0 else None, V, sg_V, use, lr, lam[1], lam[2])
                     continue
                 if xb.dense is not None:
-                    rows = torch.arange(xb.nrows, device=dev).repeat_interleave(vec_size)
-                    cols = torch.arange(vec_size, device=dev).repeat(xb.nrows)
-                    vals = xb.dense.reshape(-1)
+                    G, Gl = _coord_sums_dense(xb.dense, g, vx, sw[idx], w, V, lam, dim, use, sg_V, sg_w)
                 else:
-                    rows, cols, vals = xb.row_ids(), xb.col, xb.val
-                use.index_add_(0, cols, sw[idx][rows])
-                gr = g[rows]
+                    G, Gl = _coord_sums_scatter(xb.row_ids(), xb.col, xb.val, g, vx, sw[idx], w, V, lam, dim,
+                                                use, sg_V, sg_w)
                 if dim[2] > 0:
-                    Vc = V[cols]
-                    gv = (gr * vals)[:, None] * (vx[rows] - vals[:, None] * Vc) + lam[2] * Vc
-                    G = torch.zeros_like(V).index_add_(0, cols, gv)
-                    sg_V.index_add_(0, cols, gv * gv)
                     V = V - lr * G / torch.sqrt(sg_V + EPS)
                 if dim[1] > 0:
-                    gl = gr * vals + lam[1] * w[cols]
-                    Gl = torch.zeros_like(w).index_add_(0, cols, gl)
-                    sg_w.index_add_(0, cols, gl * gl)
                     w = w - lr * Gl / torch.sqrt(sg_w + EPS)
         # ---- model averaging (UpdateGlobalModel): one all-reduce of usage-weighted state ----
         parts = [use]

@@ -45,10 +45,18 @@ __device__ __forceinline__ int cswz(int row, int ch) {
 }
 
 // packed score for the counts-mode argmax: the lane-local candidate index li (16 * block + r, < 128) replaces the
-// low 7 mantissa bits, as 127 - li so equal truncated scores prefer the lower index; one v_max3 then reduces
-// three scores at once (the Lloyd kernel's trick, kmeans_v10.hip pack)
+// low 7 mantissa bits; one v_max3 then reduces three scores at once (the Lloyd kernel's trick, kmeans_v10.hip
+// pack).  Equal truncated scores must prefer the lower index: a larger field is the larger float only for a
+// positive score (for a negative one the larger mantissa is the more negative number), so the field is 127 - li
+// when the sign bit is clear and li when it is set (unpack_li inverts it).  li rises with the candidate index
+// inside a lane; the two half-waves are merged on the truncated score and the decoded index (the kernel).
 __device__ __forceinline__ float pack_li(float v, uint32_t li) {
-    return __uint_as_float((__float_as_uint(v) & 0xFFFFFF80u) | (127u - li));
+    const uint32_t b = __float_as_uint(v);
+    return __uint_as_float((b & 0xFFFFFF80u) | ((int32_t)b < 0 ? li : 127u - li));
+}
+
+__device__ __forceinline__ int unpack_li(uint32_t bits) {
+    return (int32_t)bits < 0 ? (int)(bits & 127u) : 127 - (int)(bits & 127u);
 }
 
 __device__ __forceinline__ float max3f(float a, float b, float c) {
@@ -203,8 +211,11 @@ __global__ __launch_bounds__(256, LAG ? 1 : 2) void kmeans_nearest_kernel(
                 // decode the lane's winner (the sentinel = every score NaN: counted nowhere), then merge the halves
                 const uint32_t bits = __float_as_uint(best[q]);
                 if (bits != __float_as_uint(kPkNone)) {
-                    const int li = 127 - (int)(bits & 127u), bb = li >> 4, r = li & 15;
+                    const int li = unpack_li(bits), bb = li >> 4, r = li & 15;
                     bidx[q] = 32 * bb + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    // the other half-wave's li order is not the candidate order: compare the truncated scores
+                    // alone below, so that equal ones fall through to the candidate index
+                    best[q] = __uint_as_float(bits & 0xFFFFFF80u);
                 }
             }
             float bq = best[q];

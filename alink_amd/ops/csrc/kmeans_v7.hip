@@ -85,8 +85,13 @@ __device__ __forceinline__ void stage(char* lds, int slot, const char* X, int64_
     }
 }
 
-__device__ __forceinline__ float pack_max(float best, float v, uint32_t c) {
-    return fmaxf(best, __uint_as_float((__float_as_uint(v) & 0xFFFFFF80u) | c));
+// Packed argmax: `field` replaces the 7 low mantissa bits of a score and a float max keeps the best score with,
+// in its low bits, which centroid had it.  Between scores equal in their top 25 bits the larger field wins when
+// they are positive and loses when they are negative, and ties must go to the lowest index as on every other
+// path: the main pass packs 127 - c (right for a row whose best score is >= +0), and a row whose best score has
+// the sign bit set is redone with field c (the kernel's rare second pass; same rule as kmeans_v10.hip pack).
+__device__ __forceinline__ float pack_max(float best, float v, uint32_t field) {
+    return fmaxf(best, __uint_as_float((__float_as_uint(v) & 0xFFFFFF80u) | field));
 }
 
 template <int KB, int MODE, int VAR>
@@ -187,14 +192,27 @@ __global__ __launch_bounds__(512) void kmeans_v7_kernel(const __bf16* __restrict
 #pragma unroll
             for (int b = 0; b < KB; ++b)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) best = pack_max(best, acc[b][r], (uint32_t)(16 * b + 4 * g + r));
+                for (int r = 0; r < 4; ++r) best = pack_max(best, acc[b][r], 127u - (uint32_t)(16 * b + 4 * g + r));
             best = fmaxf(best, __shfl_xor(best, 16));
             best = fmaxf(best, __shfl_xor(best, 32));
+            uint32_t c = 127u - (__float_as_uint(best) & 127u);
+            // rows whose best score has the sign bit set (see pack_max): the whole wave redoes the reduction
+            // with field c when one of its 16 rows is such a row (a uniform branch); the other rows keep c
+            const bool negrow = (int32_t)__float_as_uint(best) < 0;
+            if (__builtin_amdgcn_ballot_w64(negrow) != 0) {
+                float bn = -3.4e38f;
+#pragma unroll
+                for (int b = 0; b < KB; ++b)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) bn = pack_max(bn, acc[b][r], (uint32_t)(16 * b + 4 * g + r));
+                bn = fmaxf(bn, __shfl_xor(bn, 16));
+                bn = fmaxf(bn, __shfl_xor(bn, 32));
+                if (negrow) c = __float_as_uint(bn) & 127u;
+            }
             if (g == 0) {
                 uint16_t* oh = reinterpret_cast<uint16_t*>(lds + OFF_OH + (int)(i & 1) * OHB);
                 if (prev2 != NONE) oh[ohoff((int)prev2, myrow) >> 1] = 0;
                 const int64_t grow = (tbase + i) * TR + myrow;
-                const uint32_t c = __float_as_uint(best) & 127u;
                 prev2 = prev1;
                 prev1 = NONE;
                 if (grow < N) {

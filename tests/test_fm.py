@@ -72,3 +72,40 @@ def test_generic_fm_ops_equal_task_specific_ops():
                                    .setNumFactor(3).setLearnRate(0.05)).collect()
     with pytest.raises(ValueError):
         src.link(FmTrainBatchOp().setVectorCol("vec").setLabelCol("y"))
+
+
+def test_dense_batch_reduction_equals_the_scatter_formulation():
+    """One dense micro-batch: the per-coordinate sums as reductions over the batch axis (``_coord_sums_dense``)
+    against the scatter over the full (row, column) grid they replace, to 1e-12 relative (fp64 sums of 64 terms
+    in two orders differ by at most 2 * 64 * 2^-53 sum|terms|, four orders of magnitude below that)."""
+    import torch
+    from alink_amd.models.recommendation.fm import _coord_sums_dense, _coord_sums_scatter
+    g = torch.Generator().manual_seed(1)
+    m, vec, k = 64, 9, 4
+    X = torch.randn(m, vec, generator=g, dtype=torch.float64)
+    gg, vx = torch.randn(m, generator=g, dtype=torch.float64), torch.randn(m, k, generator=g, dtype=torch.float64)
+    sw = torch.rand(m, generator=g, dtype=torch.float64)
+    w, V = torch.randn(vec, generator=g, dtype=torch.float64), torch.randn(vec, k, generator=g, dtype=torch.float64)
+    lam, dim = [0.0, 0.1, 0.2], [1, 1, k]
+
+    def accs():
+        return [torch.full((vec,), 0.5, dtype=torch.float64), torch.ones(vec, k, dtype=torch.float64),
+                torch.ones(vec, dtype=torch.float64)]
+    a, b = accs(), accs()
+    Ga, Gla = _coord_sums_dense(X, gg, vx, sw, w, V, lam, dim, *a)
+    rows = torch.arange(m).repeat_interleave(vec)
+    cols = torch.arange(vec).repeat(m)
+    Gb, Glb = _coord_sums_scatter(rows, cols, X.reshape(-1), gg, vx, sw, w, V, lam, dim, *b)
+    for x, y in zip([Ga, Gla] + a, [Gb, Glb] + b):
+        assert x.shape == y.shape
+        assert float((x - y).abs().max()) <= 1e-12 * float(y.abs().max())
+    # the linear-only and factor-only configurations take the same two routes
+    for dm in ([1, 1, 0], [1, 0, k]):
+        a, b = accs(), accs()
+        ra = _coord_sums_dense(X, gg, vx if dm[2] else None, sw, w if dm[1] else None, V if dm[2] else None, lam, dm, *a)
+        rb = _coord_sums_scatter(rows, cols, X.reshape(-1), gg, vx if dm[2] else None, sw, w if dm[1] else None,
+                                 V if dm[2] else None, lam, dm, *b)
+        for x, y in zip(list(ra) + a, list(rb) + b):
+            assert (x is None) == (y is None)
+            if x is not None:
+                assert float((x - y).abs().max()) <= 1e-12 * float(y.abs().max())
