@@ -4,7 +4,9 @@
 first tile pair is published, at the end of its distance / accumulate loops, after the fold of the four wave-private
 sums and at exit.  Prints, per row count and direction (forward / serpentine-reverse), the distribution over
 workgroups of each phase and the kernel span (first entry -> last exit), so the per-launch fixed cost (ramp, fold,
-straggler tail) can be read off directly.
+straggler tail) can be read off directly.  ``pre_wait`` is the per-role split of the main loop: the share of its
+shader-clock cycles that wave 0 (distance role) and wave 4 (loader / accumulate role) spend parked in the vmcnt wait
+and in the barrier of every iteration.  The role whose barrier share is near zero arrives last: it is the pole.
 
     ALINK_HIP_LIB=variants/libalink_hip_timing.so python tools/kmeans_wg_timing.py --rows 12500000,100000000
 """
@@ -58,7 +60,18 @@ def main():
                 torch.cuda.synchronize()
                 wall = (time.perf_counter() - t0) * 1e3
             grid = K._GRID[("v10", r, None, X.device.index)]
-            st = stamps[:16 * grid].view(torch.int64).view(grid, 8).cpu().numpy().astype(np.float64) * 0.01  # us
+            raw = stamps[:32 * grid].view(torch.int64).view(grid, 16).cpu().numpy().astype(np.float64)
+            st = raw[:, :8] * 0.01  # us
+            # per-role wait split (shader-clock cycles of wave 0 / wave 4, summed over the launch): the share of
+            # the main loop spent in pre(j)'s vmcnt wait and in its barrier
+            waits = {}
+            for role, o in (("dist", 8), ("acc", 11)):
+                loop = np.maximum(raw[:, o + 2], 1.0)
+                waits[role] = {"loop_Mcyc": _q(raw[:, o + 2] * 1e-6),
+                               "vmcnt_wait_pct": _q(100.0 * raw[:, o] / loop),
+                               "barrier_wait_pct": _q(100.0 * raw[:, o + 1] / loop),
+                               "sum_vmcnt_wait_pct": round(float(100.0 * raw[:, o].sum() / loop.sum()), 2),
+                               "sum_barrier_wait_pct": round(float(100.0 * raw[:, o + 1].sum() / loop.sum()), 2)}
             t0 = st[:, 0].min()
             rel = st[:, :6] - t0
             res = {"rows": r, "rev": rev, "grid": grid, "wall_ms_last": round(wall, 4),
@@ -70,6 +83,7 @@ def main():
                    "fold_us": _q(st[:, 4] - np.maximum(st[:, 2], st[:, 3])),
                    "slab_write_us": _q(st[:, 5] - st[:, 4]),
                    "exit_us": _q(rel[:, 5]),
+                   "pre_wait": waits,
                    "slowest_wgs": [int(i) for i in np.argsort(-rel[:, 5])[:8]]}
             print(json.dumps(res), flush=True)
 
