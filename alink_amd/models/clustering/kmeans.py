@@ -28,6 +28,10 @@ Sparse vector columns (a ``SparseBlock``, sparse vectors or sparse vector string
 cover train and predict as CSR rows (``ops/kmeans_sparse.py``, ``csrc/kmeans_sparse.hip``): the reference clusters
 ``SparseVector``s the same way (``KMeansUtil.updateSumMatrix``, ``KMeansUtil.java:76-83``).  EUCLIDEAN and COSINE;
 only candidate centroid rows are ever densified.
+
+fp64 rows of any vector size up to 1024 (what an ordinary vector column is on the device) take
+``ops/kmeans_dense64.py`` (``csrc/kmeans_dense64.hip``) for the Lloyd step, the k-means|| distance and weights
+passes and id-only prediction, EUCLIDEAN and COSINE; ``ALINK_KMEANS_DENSE64=0`` restores the torch path.
 """
 from __future__ import annotations
 
@@ -49,7 +53,7 @@ from ...params import get_enum, param
 from ...parallel import comm
 from ...parallel.comqueue import (AllReduce, CompareCriterionFunction, CompleteResultFunction, ComputeFunction,
                                   IterativeComQueue)
-from ...ops import _lib, kmeans as kops, kmeans_sparse as ksp
+from ...ops import _lib, kmeans as kops, kmeans_dense64 as kd64, kmeans_sparse as ksp
 
 __all__ = ["ClusterSummary", "KMeansTrainModelData", "KMeansModelDataConverter", "KMeansPredictModelData",
            "KMeansModelMapper", "train_kmeans", "kmeans_init", "pairwise_distance"]
@@ -203,9 +207,19 @@ def _hip_nearest_ok(X: torch.Tensor, dist_type: str) -> bool:
     return dist_type.upper() == "EUCLIDEAN" and kops.nearest_supported(X) and _lib.available()
 
 
+def _dense64_ok(X, k: int, dist_type: str) -> bool:
+    """fp64 device rows that ``ops/kmeans_dense64.py`` takes (EUCLIDEAN / COSINE; an empty partition launches
+    nothing and stays on the torch path)."""
+    return (not _is_sparse(X) and dist_type.upper() in ("EUCLIDEAN", "COSINE") and kd64.dense64_selected(X, k)
+            and X.shape[0] > 0)
+
+
 def _min_dist_to(X: torch.Tensor, C: torch.Tensor, dist_type: str, chunk=1 << 20) -> torch.Tensor:
     if _is_sparse(X):
         dist = ksp.nearest(X, C, dist_type)[1]
+        return dist.sqrt_() if dist_type.upper() == "EUCLIDEAN" else dist
+    if _dense64_ok(X, C.shape[0], dist_type):
+        dist = kd64.nearest(X, C, dist_type)[1]
         return dist.sqrt_() if dist_type.upper() == "EUCLIDEAN" else dist
     if _hip_nearest_ok(X, dist_type):
         if C.shape[0] == 1:      # the first k-means|| cost: one streaming pass, fp64 distances straight out
@@ -222,6 +236,8 @@ def _min_dist_to(X: torch.Tensor, C: torch.Tensor, dist_type: str, chunk=1 << 20
 def _nearest(X: torch.Tensor, C: torch.Tensor, dist_type: str, chunk=1 << 20) -> torch.Tensor:
     if _is_sparse(X):
         return ksp.nearest(X, C, dist_type)[0]
+    if _dense64_ok(X, C.shape[0], dist_type):
+        return kd64.nearest(X, C, dist_type)[0]
     if _hip_nearest_ok(X, dist_type):
         return kops.nearest_hip(X, C)[0].to(torch.int64)
     out = []
@@ -478,6 +494,8 @@ def kmeans_init(X: torch.Tensor, k: int, init_mode: str, init_steps: int, dist_t
         w = kops.nearest_counts_hip(X, centers).to(torch.float64)      # one pass, no per-row output
     elif _is_sparse(X):
         w = ksp.nearest_counts(X, centers, dist_type).to(torch.float64)
+    elif _dense64_ok(X, centers.shape[0], dist_type):
+        w = kd64.nearest_counts(X, centers, dist_type).to(torch.float64)
     else:
         w = torch.bincount(_nearest(X, centers, dist_type), minlength=centers.shape[0]).to(torch.float64)
     comm.all_reduce(w)
@@ -922,6 +940,11 @@ class KMeansModelMapper(ModelMapper):
             if dt == "COSINE":
                 Xf = _normalize_rows(Xf)
             C = self.C.to(Xf.device)
+            if not self.detail_col and C.dim() == 2 and C.shape[0] >= 1 and C.shape[1] == Xf.shape[1] and \
+                    _dense64_ok(Xf.contiguous(), C.shape[0], dt):
+                # only the id (and its distance) is asked for: no [n, k] distance matrix
+                idx, best = kd64.nearest(Xf.contiguous(), C, dt)
+                return idx, (best.sqrt_() if dt == "EUCLIDEAN" else best), None, nulls
             dist_all = pairwise_distance(Xf, C, dt)
             best, idx = dist_all.min(1)
         return idx, best, dist_all, nulls

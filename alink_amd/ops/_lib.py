@@ -168,6 +168,10 @@ _SIGNATURES = {
                                     _c_vp, _c_vp, _c_vp, _c_int, _c_vp],
     "alink_kmeans_sparse_accum": [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp,
                                   _c_int, _c_vp, _c_vp, _c_int, _c_vp],
+    "alink_kmeans_dense64_nearest": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_vp,
+                                     _c_vp, _c_vp, _c_int, _c_vp],
+    "alink_kmeans_dense64_accum": [_c_vp, _c_int, _c_vp, _c_i64, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp,
+                                   _c_vp, _c_int, _c_vp],
 }
 
 

@@ -20,6 +20,9 @@ all-reduce.
 * sparse rows (a CSR ``FeatureMatrix``) do not come through this module: ``ops/kmeans_sparse.py`` assigns and sums
   them in fp64 without densifying (``csrc/kmeans_sparse.hip``; selected by ``models/clustering/kmeans.py`` and the
   operators for sparse vector columns wider than the dense kernels cover).
+* GPU, fp64 rows of any d up to 1024 (vector columns, VectorAssembler output), any k, unweighted:
+  ``ops/kmeans_dense64.py`` (``csrc/kmeans_dense64.hip``) — fp64 MFMA scores + argmax, then per-cluster sums in a
+  fixed order without float atomics; exact fp64, ``ALINK_KMEANS_DENSE64=0`` turns it off.
 * anything else: chunked PyTorch path (fp64 on CPU; on GPU fp32 GEMM of the same bf16-rounded centroids).
 """
 from __future__ import annotations
@@ -32,6 +35,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import kmeans_dense64 as _d64
 
 __all__ = ["assign_accumulate", "assign", "assign_accumulate_torch", "hip_supported", "prepare_centroids",
            "general_supported", "assign_accumulate_general_hip", "accumulate_by_index_hip", "f32_supported",
@@ -635,6 +639,8 @@ def assign_accumulate(X: torch.Tensor, C: torch.Tensor, weights: Optional[torch.
     if weights is None and hip_supported(X, C.shape[0]) and hip_ok:
         return assign_accumulate_hip(X, C, reverse=reverse)
     with _timed(X.device):
+        if weights is None and _d64.dense64_selected(X, C.shape[0]) and X.shape[0] > 0:
+            return _d64.assign_accumulate(X, C)     # raises without the library unless the fall-back is allowed
         if general_supported(X, C.shape[0]) and hip_ok:
             return assign_accumulate_general_hip(X, C, weights)
         if f32_supported(X, C.shape[0]) and hip_ok:

@@ -33,7 +33,7 @@ __all__ = ["ACCUM_CHUNK", "sparse_supported", "sparse_selected", "prepare", "nea
 
 ACCUM_CHUNK = 512       # entries of one column that one wave sums; longer columns are split and merged in order
 DENSE_DMAX = 1024       # the largest d a dense HIP KMeans kernel covers (ops/kmeans.py): sparse input wider than
-                        # this takes the sparse path
+                        # this takes the sparse path.  It is also the dense fp64 limit (ops/kmeans_dense64.py)
 SPARSE_CALLS = 0        # launches of the HIP sparse path (tests read it)
 TORCH_CHUNK = 1 << 14   # rows per chunk of the torch path
 
