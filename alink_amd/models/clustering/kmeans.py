@@ -19,24 +19,13 @@ Reference behaviour (cited per piece):
 * predict — ``KMeansModelMapper.java:61-97``: prediction (cluster id), optional detail
   (``KMeansUtil.getProbArrayFromDistanceArray``) and distance columns.
 
-MI355X path: rows stay on the GPU; the assign/accumulate step is the fused HIP kernel
-(``ops/csrc/kmeans_v10.hip`` for bf16 rows with d = 128, ``kmeans_accum.hip`` for other bf16 shapes, see
-``ops/kmeans.py``), the [k, d+1] all-reduce is the one-shot xGMI kernel (``ops/csrc/allreduce.hip``) or RCCL,
-and the update/criterion is one fused HIP kernel (``kmeans_common.hip``) — no per-sample host work.
-
-Sparse vector columns (a ``SparseBlock``, sparse vectors or sparse vector strings) wider than the dense kernels
-cover train and predict as CSR rows (``ops/kmeans_sparse.py``, ``csrc/kmeans_sparse.hip``): the reference clusters
-``SparseVector``s the same way (``KMeansUtil.updateSumMatrix``, ``KMeansUtil.java:76-83``).  EUCLIDEAN and COSINE;
-only candidate centroid rows are ever densified.
-
-fp64 rows of any vector size up to 1024 (what an ordinary vector column is on the device) take
-``ops/kmeans_dense64.py`` (``csrc/kmeans_dense64.hip``) for the Lloyd step, the k-means|| distance and weights
-passes and id-only prediction, EUCLIDEAN and COSINE; ``ALINK_KMEANS_DENSE64=0`` restores the torch path.
+MI355X path: rows stay on the GPU behind the rows object of ``ops/kmeans_rows.py``, which chooses a run's kernel family
+once (fused bf16, dense fp64, CSR or torch; described there); the [k, d+1] all-reduce is the one-shot xGMI kernel
+(``ops/csrc/allreduce.hip``) or RCCL, the update/criterion one fused HIP kernel (``kmeans_common.hip``).
 """
 from __future__ import annotations
 
 import json
-import math
 import os
 from typing import List, Optional
 
@@ -53,7 +42,8 @@ from ...params import get_enum, param
 from ...parallel import comm
 from ...parallel.comqueue import (AllReduce, CompareCriterionFunction, CompleteResultFunction, ComputeFunction,
                                   IterativeComQueue)
-from ...ops import _lib, kmeans as kops, kmeans_dense64 as kd64, kmeans_sparse as ksp
+from ...ops import _lib, kmeans as kops, kmeans_rows as krows
+from ...ops.kmeans_rows import pairwise_distance
 
 __all__ = ["ClusterSummary", "KMeansTrainModelData", "KMeansModelDataConverter", "KMeansPredictModelData",
            "KMeansModelMapper", "train_kmeans", "kmeans_init", "pairwise_distance"]
@@ -137,61 +127,9 @@ class KMeansModelDataConverter(SimpleModelDataConverter):
 # ---------------------------------------------------------------------------------------------------
 # distances
 # ---------------------------------------------------------------------------------------------------
-def pairwise_distance(X: torch.Tensor, C: torch.Tensor, distance_type: str) -> torch.Tensor:
-    """[n, k] FastDistance values (EUCLIDEAN: sqrt|x-c|^2, COSINE: 1 - x.c on normalised inputs,
-    HAVERSINE: great-circle km on (lat, lon) degrees)."""
-    dt = distance_type.upper()
-    if dt == "COSINE":
-        return 1.0 - X @ C.T
-    if dt == "HAVERSINE":
-        lat1 = torch.deg2rad(X[:, 0:1])
-        lon1 = torch.deg2rad(X[:, 1:2])
-        lat2 = torch.deg2rad(C[:, 0])[None, :]
-        lon2 = torch.deg2rad(C[:, 1])[None, :]
-        a = torch.sin((lat2 - lat1) / 2) ** 2 + torch.cos(lat1) * torch.cos(lat2) * torch.sin((lon2 - lon1) / 2) ** 2
-        return 2 * 6371.0 * torch.asin(torch.sqrt(a.clamp(0, 1)))
-    xn = (X * X).sum(1, keepdim=True)
-    cn = (C * C).sum(1)[None, :]
-    return torch.sqrt((xn + cn - 2.0 * (X @ C.T)).abs())
-
-
 def _normalize_rows(X: torch.Tensor) -> torch.Tensor:
     n = X.norm(dim=1, keepdim=True)
     return torch.where(n > 0, X / torch.where(n > 0, n, torch.ones_like(n)), X)
-
-
-# ---------------------------------------------------------------------------------------------------
-# sparse rows (a CSR ``FeatureMatrix``, ``ops/kmeans_sparse.py``): never densified as a whole
-# ---------------------------------------------------------------------------------------------------
-def _is_sparse(X) -> bool:
-    return not isinstance(X, torch.Tensor)
-
-
-def _nrows(X) -> int:
-    return int(X.nrows) if _is_sparse(X) else int(X.shape[0])
-
-
-def _sparse_view(fm, ncols: int, val: Optional[torch.Tensor] = None):
-    """The same CSR arrays as ``fm`` (or other values) under ``ncols`` columns, as a new FeatureMatrix."""
-    from ..common.features import FeatureMatrix
-    return FeatureMatrix(crow=fm.crow, col=fm.col, val=fm.val if val is None else val, ncols=int(ncols))
-
-
-def _normalize_sparse(fm, d: int):
-    """COSINE row normalisation of CSR rows: ``val`` scaled by the row norm over the columns inside [0, d); zero
-    rows stay as they are, as ``_normalize_rows`` leaves them."""
-    if fm.nrows == 0 or fm.val.numel() == 0:
-        return _sparse_view(fm, d)
-    nrm = ksp.row_sqnorm(fm, d).sqrt_()
-    nrm = torch.where(nrm > 0, nrm, torch.ones_like(nrm))
-    return _sparse_view(fm, d, fm.val / nrm[fm.row_ids()])
-
-
-def _rows_dense(X, idx: torch.Tensor) -> torch.Tensor:
-    """The few rows ``idx`` as a dense fp64 block (candidate centroids)."""
-    if _is_sparse(X):
-        return ksp.take_dense(X, idx)
-    return X[idx].to(torch.float64)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -199,53 +137,6 @@ def _rows_dense(X, idx: torch.Tensor) -> torch.Tensor:
 # ---------------------------------------------------------------------------------------------------
 def _seed_cost(d: torch.Tensor, dist_type: str) -> torch.Tensor:
     return d * d if dist_type.upper() == "EUCLIDEAN" else d
-
-
-def _hip_nearest_ok(X: torch.Tensor, dist_type: str) -> bool:
-    if _is_sparse(X):
-        return False
-    return dist_type.upper() == "EUCLIDEAN" and kops.nearest_supported(X) and _lib.available()
-
-
-def _dense64_ok(X, k: int, dist_type: str) -> bool:
-    """fp64 device rows that ``ops/kmeans_dense64.py`` takes (EUCLIDEAN / COSINE; an empty partition launches
-    nothing and stays on the torch path)."""
-    return (not _is_sparse(X) and dist_type.upper() in ("EUCLIDEAN", "COSINE") and kd64.dense64_selected(X, k)
-            and X.shape[0] > 0)
-
-
-def _min_dist_to(X: torch.Tensor, C: torch.Tensor, dist_type: str, chunk=1 << 20) -> torch.Tensor:
-    if _is_sparse(X):
-        dist = ksp.nearest(X, C, dist_type)[1]
-        return dist.sqrt_() if dist_type.upper() == "EUCLIDEAN" else dist
-    if _dense64_ok(X, C.shape[0], dist_type):
-        dist = kd64.nearest(X, C, dist_type)[1]
-        return dist.sqrt_() if dist_type.upper() == "EUCLIDEAN" else dist
-    if _hip_nearest_ok(X, dist_type):
-        if C.shape[0] == 1:      # the first k-means|| cost: one streaming pass, fp64 distances straight out
-            return kops.cost1_hip(X, C[0])
-        return kops.nearest_hip(X, C)[1].to(torch.float64).sqrt_()
-    out = []
-    Cf = C.to(torch.float32 if X.dtype in (torch.bfloat16, torch.float16) else X.dtype)
-    for s in range(0, X.shape[0], chunk):
-        xc = X[s:s + chunk].to(Cf.dtype)
-        out.append(pairwise_distance(xc, Cf, dist_type).min(1).values.to(torch.float64))
-    return torch.cat(out) if out else torch.zeros(0, dtype=torch.float64, device=X.device)
-
-
-def _nearest(X: torch.Tensor, C: torch.Tensor, dist_type: str, chunk=1 << 20) -> torch.Tensor:
-    if _is_sparse(X):
-        return ksp.nearest(X, C, dist_type)[0]
-    if _dense64_ok(X, C.shape[0], dist_type):
-        return kd64.nearest(X, C, dist_type)[0]
-    if _hip_nearest_ok(X, dist_type):
-        return kops.nearest_hip(X, C)[0].to(torch.int64)
-    out = []
-    Cf = C.to(torch.float32 if X.dtype in (torch.bfloat16, torch.float16) else X.dtype)
-    for s in range(0, X.shape[0], chunk):
-        xc = X[s:s + chunk].to(Cf.dtype)
-        out.append(pairwise_distance(xc, Cf, dist_type).argmin(1))
-    return torch.cat(out) if out else torch.zeros(0, dtype=torch.int64, device=X.device)
 
 
 def _global_count(n_local: int) -> List[int]:
@@ -276,22 +167,17 @@ def _row_uniform(first_row: int, n: int, seed: int, rnd: int, device) -> torch.T
     return (_shr(z, 11).to(torch.float64) + 0.5) * (1.0 / (1 << 53))
 
 
-def _fetch_global_rows(X: torch.Tensor, global_idx: List[int], counts: List[int]) -> torch.Tensor:
-    """Rows by global index (rank-order concatenation), replicated on every rank: each rank writes the rows
+def _fetch_global_rows(X, global_idx: List[int], counts: List[int]) -> torch.Tensor:
+    """Rows of the rows object ``X`` by global index (rank order), replicated on every rank: each rank writes the rows
     it owns into a zero [m, d] fp64 block and one SUM all-reduce (RCCL on GPU) assembles it — no pickling."""
     rank = comm.get_rank()
     offs = np.concatenate([[0], np.cumsum(counts)])
-    if _is_sparse(X):
-        d = max(1, int(X.ncols))
-    else:
-        d = max(1, int(X.shape[1])) if X.dim() == 2 else 1
-    out = torch.zeros((len(global_idx), d), dtype=torch.float64, device=X.device)
+    out = torch.zeros((len(global_idx), max(1, X.d)), dtype=torch.float64, device=X.device)
     mine = [(j, g - offs[rank]) for j, g in enumerate(global_idx) if offs[rank] <= g < offs[rank + 1]]
     if mine:
         dst = torch.as_tensor([j for j, _ in mine], dtype=torch.long, device=X.device)
         src = torch.as_tensor([int(i) for _, i in mine], dtype=torch.long, device=X.device)
-        out.index_copy_(0, dst, _rows_dense(X, src) if _is_sparse(X) else
-                        X.index_select(0, src).to(torch.float64))
+        out.index_copy_(0, dst, X.take(src))
     comm.all_reduce(out)
     return out
 
@@ -379,7 +265,6 @@ def _local_kmeans(samples: torch.Tensor, weights: torch.Tensor, k: int, dist_typ
     per-centroid or per-pick host read — one 2-flag read per Lloyd iteration (changed assignment, empty cluster);
     an empty cluster is refilled from a random candidate in ascending cluster order, as before.  On the GPU the
     cluster sums are a one-hot fp64 GEMM (run-to-run deterministic)."""
-    import os
     rng = np.random.default_rng(seed)
     n = samples.shape[0]
     w = weights.to(torch.float64)
@@ -450,10 +335,11 @@ def _local_kmeans(samples: torch.Tensor, weights: torch.Tensor, k: int, dist_typ
     return C
 
 
-def kmeans_init(X: torch.Tensor, k: int, init_mode: str, init_steps: int, dist_type: str,
-                seed: int = 0) -> torch.Tensor:
-    """Initial centroids [k', d] float64 (identical on every rank)."""
-    counts = _global_count(_nrows(X))
+def kmeans_init(X, k: int, init_mode: str, init_steps: int, dist_type: str, seed: int = 0) -> torch.Tensor:
+    """Initial centroids [k', d] float64 (identical on every rank) for this rank's rows ``X``: a tensor, a sparse
+    ``FeatureMatrix`` or their rows object (``ops/kmeans_rows.py``)."""
+    X = krows.rows(X, dist_type)
+    counts = _global_count(X.n)
     n = int(sum(counts))
     if n == 0:
         raise ValueError("The train dataset is empty!")
@@ -463,41 +349,29 @@ def kmeans_init(X: torch.Tensor, k: int, init_mode: str, init_steps: int, dist_t
         return _fetch_global_rows(X, gidx, counts)
     # k-means||
     centers = _fetch_global_rows(X, [int(rng.integers(n))], counts)
-    psum = None
-    if _hip_nearest_ok(X, dist_type):
-        # the first cost pass also leaves per-wave sums: the threshold's total without a second pass over cost
-        cost, psum = kops.cost1_hip(X, centers[0], with_sum=True)
-    else:
-        cost = _min_dist_to(X, centers, dist_type)
+    cost, local = X.first_cost(centers)
     first_row = int(sum(counts[:comm.get_rank()]))
     rounds = max(0, init_steps - 1)
     for rnd in range(rounds):
-        local = psum.sum() if psum is not None else cost.sum()
-        psum = None
+        if rnd:
+            local = cost.sum()
         tot = torch.tensor([float(local.item())], dtype=torch.float64)
         comm.all_reduce(tot)
         thre = 2.0 * k / max(float(tot.item()), 1e-300)
         if cost.is_cuda and _lib.available():
             pick = kops.par_pick_hip(cost, first_row, _round_key(seed, rnd), thre)
         else:
-            u = _row_uniform(first_row, _nrows(X), seed, rnd, X.device)
+            u = _row_uniform(first_row, X.n, seed, rnd, X.device)
             pick = torch.nonzero(u < cost * thre).reshape(-1)
-        new = comm.all_gather_varlen(_rows_dense(X, pick))   # rank order == global row order
+        new = comm.all_gather_varlen(X.take(pick))   # rank order == global row order
         if new.shape[0] == 0:
             continue
         centers = torch.cat([centers, new])
         if rnd + 1 < rounds:           # the last round's costs would never be read: no pass over X for them
-            cost = torch.minimum(cost, _min_dist_to(X, new, dist_type))
+            cost = torch.minimum(cost, X.nearest(new)[1])
     if centers.shape[0] <= k:
         return centers
-    if _hip_nearest_ok(X, dist_type):
-        w = kops.nearest_counts_hip(X, centers).to(torch.float64)      # one pass, no per-row output
-    elif _is_sparse(X):
-        w = ksp.nearest_counts(X, centers, dist_type).to(torch.float64)
-    elif _dense64_ok(X, centers.shape[0], dist_type):
-        w = kd64.nearest_counts(X, centers, dist_type).to(torch.float64)
-    else:
-        w = torch.bincount(_nearest(X, centers, dist_type), minlength=centers.shape[0]).to(torch.float64)
+    w = X.nearest_counts(centers).to(torch.float64)
     comm.all_reduce(w)
     return _local_kmeans(centers, w, k, dist_type, seed=seed)
 
@@ -516,29 +390,17 @@ class KMeansPreallocateCentroid(ComputeFunction):
 
 class KMeansAssignCluster(ComputeFunction):
     def __init__(self, dist_type: str = "EUCLIDEAN"):
-        self.dist_type = dist_type      # read by the sparse path alone (the dense kernels score by |x - c|^2)
+        self.dist_type = dist_type
 
     def calc(self, ctx):
         cur = ctx.getObj(CENTROID1) if ctx.getStepNo() % 2 == 0 else ctx.getObj(CENTROID2)
-        k = ctx.getObj(K)
-        X = ctx.getObj(TRAIN_DATA)
-        C = cur[1][:k]
+        C = cur[1][:ctx.getObj(K)]
         spec = ctx.getObj(SPEC_BUF)
         ctx.removeObj(SPEC_BUF)
         if spec is not None and spec[0][0] == ctx.getStepNo() and kops.key_matches(spec[0][1], C):
             ctx.putObj(CENTROID_ALL_REDUCE, spec[1])    # launched by the previous superstep's update
             return
-        if X is None or _nrows(X) == 0:
-            buf = torch.zeros((k, C.shape[1] + 1), dtype=torch.float64, device=C.device)
-        elif _is_sparse(X):
-            buf = ksp.assign_accumulate(X, C, self.dist_type)
-        else:
-            buf = kops.assign_accumulate(X, C, reverse=kops.serpentine_reverse(ctx.getStepNo()))
-        ctx.putObj(CENTROID_ALL_REDUCE, buf)
-
-
-def _lib_ok() -> bool:
-    return kops._lib.available()
+        ctx.putObj(CENTROID_ALL_REDUCE, ctx.getObj(TRAIN_DATA).assign_accumulate(C, ctx.getStepNo()))
 
 
 SPEC_BUF = "speculativeAllReduceBuf"
@@ -569,11 +431,8 @@ class KMeansUpdateCentroids(ComputeFunction):
         old = ctx.getObj(CENTROID1) if ctx.getStepNo() % 2 == 0 else ctx.getObj(CENTROID2)
         buf = ctx.getObj(CENTROID_ALL_REDUCE)
         prev = old[1] if old is not None and old[1] is not None else None
-        X = ctx.getObj(TRAIN_DATA)
-        # sparse rows never take the fused update: it queues the dense assign kernel for the next superstep
-        dense_rows = X is None or not _is_sparse(X)
-        if self.dist_type == "EUCLIDEAN" and dense_rows and kops.update_supported(buf) and \
-                (_lib_ok() or not kops._lib.torch_fallback_allowed()):
+        if self.dist_type == "EUCLIDEAN" and ctx.getObj(TRAIN_DATA).fused_update and kops.update_supported(buf) \
+                and (_lib.available() or not _lib.torch_fallback_allowed()):
             C, shift, has_empty = self._fused_update(ctx, buf, prev)
             weights = buf[:, -1]
             if has_empty:
@@ -594,15 +453,13 @@ class KMeansUpdateCentroids(ComputeFunction):
         """Fused HIP update: C, the shift vs prev, the empty flag and the next step's MFMA operands in one launch +
         one 16-byte read; the next superstep's assign kernel is queued between the launch and the read."""
         step = ctx.getStepNo()
-        X = ctx.getObj(TRAIN_DATA)
-        spec_ok = (self.speculate and step >= 2 and step < self.max_iter and step not in self.sync_steps
-                   and X is not None and X.shape[0] > 0 and kops.hip_supported(X, buf.shape[0]))
+        queue = None
+        if self.speculate and step >= 2 and step < self.max_iter and step not in self.sync_steps:
+            queue = ctx.getObj(TRAIN_DATA).queue_assign(buf.shape[0])
         C, read = kops.update_centroids_hip(buf, prev, deferred=True,
-                                            skip_tol=self.tol if spec_ok and self.tol is not None else None)
-        if spec_ok:
-            ctx.putObj(SPEC_BUF, ((step + 1, kops._ckey(C)),
-                                  kops.assign_accumulate_hip(X, C, reverse=kops.serpentine_reverse(step + 1),
-                                                             skip=read.skip)))
+                                            skip_tol=self.tol if queue is not None and self.tol is not None else None)
+        if queue is not None:
+            ctx.putObj(SPEC_BUF, ((step + 1, kops._ckey(C)), queue(C, step + 1, read.skip)))
         shift, has_empty = read()
         if has_empty or (read.skip is not None and shift is not None and shift < self.tol):
             ctx.removeObj(SPEC_BUF)     # not used (compaction) / possibly skipped on the device (converged)
@@ -710,42 +567,36 @@ class KMeansOutputModel(CompleteResultFunction):
         return KMeansModelDataConverter().save(md)
 
 
-def train_kmeans(X: torch.Tensor, k: int, max_iter: int, tol: float, dist_type: str, init_mode: str,
+def train_kmeans(X, k: int, max_iter: int, tol: float, dist_type: str, init_mode: str,
                  init_steps: int, vector_col: Optional[str], env, lat_col=None, lon_col=None,
                  init_centroids: Optional[torch.Tensor] = None, on_step=None, seed: int = 0, sync_steps=()):
-    """Run the KMeans BSP queue on this rank's rows ``X`` ([n, d] on the env device); returns
-    (model rows, queue)."""
+    """Run the KMeans BSP queue on this rank's rows ``X`` ([n, d] on the env device, or a ``FeatureMatrix`` whose
+    sparse rows are never densified as a whole); returns (model rows, queue)."""
     dist_type = dist_type.upper()
-    if _is_sparse(X) and not X.is_sparse:
+    if not isinstance(X, torch.Tensor) and not X.is_sparse:
         X = X.dense
-    if _is_sparse(X):
-        return _train_kmeans_sparse(X, k, max_iter, tol, dist_type, init_mode, init_steps, vector_col, env,
-                                    init_centroids, on_step, seed, sync_steps)
+    sparse = not isinstance(X, torch.Tensor)
     # opt-in device precision for fp64 feature matrices (VectorAssembler output): ALINK_KMEANS_INPUT=fp32 runs the
     # fp32 GEMM-assign + HIP accumulate path, =bf16 the fused bf16 MFMA kernels (a one-time cast of this rank's
     # rows; profiles/kmeans_fp32_r4.txt records the centroid deltas against fp64)
     cast = os.environ.get("ALINK_KMEANS_INPUT", "").lower()
-    if cast in ("fp32", "bf16") and X.is_cuda and X.dtype == torch.float64 and dist_type == "EUCLIDEAN":
+    if not sparse and cast in ("fp32", "bf16") and X.is_cuda and X.dtype == torch.float64 and dist_type == "EUCLIDEAN":
         X = X.to(torch.float32 if cast == "fp32" else torch.bfloat16).contiguous()
-    if dist_type == "COSINE":
+    if not sparse and dist_type == "COSINE":
         X = _normalize_rows(X.to(torch.float64)) if X.dtype == torch.float64 else \
             _normalize_rows(X.float()).to(X.dtype)
-    vs = torch.tensor([float(X.shape[1]) if X.shape[0] else 0.0], dtype=torch.float64)
+    vs = torch.tensor([float(X.ncols if sparse else X.shape[1]) if len(X) else 0.0], dtype=torch.float64)
     vector_size = int(comm.all_reduce(vs, "max").item())
+    if sparse:      # fp64 values under the global vector size, normalised for COSINE
+        X = krows.sparse_rows(X, vector_size, dist_type)
+    X = krows.rows(X, dist_type)
     init = init_centroids if init_centroids is not None else kmeans_init(X, k, init_mode, init_steps, dist_type,
                                                                          seed=seed)
-    return _run_kmeans_queue(X, init, vector_size, k, max_iter, tol, dist_type, vector_col, env, lat_col, lon_col,
-                             on_step, sync_steps)
-
-
-def _run_kmeans_queue(X, init, vector_size, k, max_iter, tol, dist_type, vector_col, env, lat_col, lon_col, on_step,
-                      sync_steps):
-    """The Lloyd BSP queue over this rank's rows ``X`` (a tensor, or a sparse FeatureMatrix) from ``init``."""
     init = init.to(device=X.device, dtype=torch.float64)
     q = (IterativeComQueue()
          .setMLEnvironment(env)
          .setJobName("KMeans")
-         .setRowsPerStep(_nrows(X))
+         .setRowsPerStep(X.n)
          .initWithPartitionedData(TRAIN_DATA, X)
          .initWithBroadcastData(INIT_CENTROID, init)
          .add(KMeansPreallocateCentroid())
@@ -761,24 +612,6 @@ def _run_kmeans_queue(X, init, vector_size, k, max_iter, tol, dist_type, vector_
         q.addStepCallback(on_step)
     rows = q.exec()
     return rows, q
-
-
-def _train_kmeans_sparse(fm, k, max_iter, tol, dist_type, init_mode, init_steps, vector_col, env, init_centroids,
-                         on_step, seed, sync_steps):
-    """``train_kmeans`` for CSR rows: the same queue, with the assignment, the sums and the k-means|| passes on
-    the sparse kernels (``ops/kmeans_sparse.py``).  Only candidate rows are ever densified."""
-    if dist_type not in ("EUCLIDEAN", "COSINE"):
-        raise ValueError(f"sparse KMeans supports EUCLIDEAN and COSINE, not {dist_type}")
-    vs = torch.tensor([float(fm.ncols) if fm.nrows else 0.0], dtype=torch.float64)
-    vector_size = int(comm.all_reduce(vs, "max").item())
-    if fm.val.dtype != torch.float64:
-        fm = _sparse_view(fm, fm.ncols, fm.val.to(torch.float64))
-    # every rank works in the global vector size (an empty partition knows no size of its own)
-    X = _normalize_sparse(fm, vector_size) if dist_type == "COSINE" else _sparse_view(fm, vector_size)
-    init = init_centroids if init_centroids is not None else kmeans_init(X, k, init_mode, init_steps, dist_type,
-                                                                         seed=seed)
-    return _run_kmeans_queue(X, init, vector_size, k, max_iter, tol, dist_type, vector_col, env, None, None, on_step,
-                             sync_steps)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -854,100 +687,45 @@ class KMeansModelMapper(ModelMapper):
 
     def _sparse_input(self, mt: MTable):
         """(sparse FeatureMatrix under the model's vector size, null flags or None) when the vector column is
-        sparse and the sparse path is selected (``ops/kmeans_sparse.sparse_selected``), else None."""
-        m = self.model
-        dt = m.distanceType.upper()
-        if m.vectorColName is None or dt not in ("EUCLIDEAN", "COSINE") or self.C.dim() != 2 or self.C.shape[0] < 1:
-            return None
-        d = int(self.C.shape[1])
-        if os.environ.get("ALINK_KMEANS_SPARSE", "") == "0" or d < 1:
+        sparse and the sparse path is selected (``ops/kmeans_rows.sparse_selected``), else None."""
+        m, d = self.model, int(self.C.shape[-1])
+        if m.vectorColName is None or m.distanceType.upper() not in ("EUCLIDEAN", "COSINE") or self.C.dim() != 2 \
+                or self.C.shape[0] < 1 or d < 1 or not krows.sparse_selected(True, d):
             return None
         c = mt.col(m.vectorColName)
         v = c.values
-        from ...common.linalg import SparseVector
         from ...common.linalg.block import SparseBlock
         from ..common.features import FeatureMatrix, _vectors_to_matrix
         if isinstance(v, SparseBlock):
-            if not ksp.sparse_selected(True, d):
-                return None
             nulls = c.nulls.cpu().tolist() if c.nulls is not None else None
             return FeatureMatrix(crow=v.crow, col=v.col, val=v.val, ncols=d), nulls
-        if isinstance(v, torch.Tensor):
-            return None
-        vals = c.to_list()
-        first = next((x for x in vals if x is not None), None)
-        if not (isinstance(first, SparseVector) or (isinstance(first, str) and ("$" in first or ":" in first))):
-            return None
-        if not ksp.sparse_selected(True, d):
+        vals = v if isinstance(v, torch.Tensor) else c.to_list()
+        if krows.column_kind(vals) != krows.SPARSE:
             return None
         fm = _vectors_to_matrix(vals, torch.float64, torch.device("cpu"), d)
-        if not fm.is_sparse:
-            return None
         nulls = [x is None for x in vals]
-        return _sparse_view(fm, d), (nulls if any(nulls) else None)
-
-    def _map_sparse(self, fm):
-        """(ids index, best distance, all distances or None) of CSR rows through ``ops/kmeans_sparse.nearest``."""
-        dt = self.model.distanceType.upper()
-        d = int(self.C.shape[1])
-        if dt == "COSINE":
-            fm = _normalize_sparse(fm, d)
-        C = self.C.to(fm.device)
-        idx, best = ksp.nearest(fm, C, dt)
-        if dt == "EUCLIDEAN":
-            best = best.sqrt()
-        dist_all = None
-        if self.detail_col:
-            # every distance, in row chunks of the CSR product (the [n, k] result is the only dense block)
-            col, val = ksp._clipped(fm, d)
-            safe = _sparse_view(fm, d, val)
-            safe.col = col
-            Ct = C.t().contiguous()
-            cn = (C * C).sum(1)[None, :]
-            xn = ksp.row_sqnorm(fm, d)
-            parts = []
-            for s in range(0, fm.nrows, 1 << 16):
-                dot = safe[s:s + (1 << 16)].mm(Ct)
-                parts.append(1.0 - dot if dt == "COSINE" else
-                             torch.sqrt((xn[s:s + (1 << 16), None] + cn - 2.0 * dot).abs()))
-            dist_all = torch.cat(parts) if parts else torch.zeros((0, C.shape[0]), dtype=torch.float64,
-                                                                  device=fm.device)
-        return idx, best, dist_all
+        return (fm, nulls if any(nulls) else None) if fm.is_sparse else None
 
     def _map_columns(self, mt: MTable):
-        sp = self._sparse_input(mt)
-        if sp is not None:
-            nulls = sp[1]
-            idx, best, dist_all = self._map_sparse(sp[0])
-        else:
-            idx, best, dist_all, nulls = self._map_dense(mt)
-        return self._outputs(idx, best, dist_all, nulls)
-
-    def _map_dense(self, mt: MTable):
-        X, nulls = self._input_block(mt)
-        dev = X.device
         dt = self.model.distanceType.upper()
-        if X.dtype in (torch.bfloat16, torch.float16) and dt == "EUCLIDEAN" and X.is_cuda:
-            C = self.C.to(dev)
+        sp = self._sparse_input(mt)
+        X, nulls = self._input_block(mt) if sp is None else (krows.sparse_rows(sp[0], int(self.C.shape[1]), dt), sp[1])
+        low = sp is None and X.is_cuda and X.dtype in (torch.bfloat16, torch.float16) and dt == "EUCLIDEAN"
+        if sp is None and not low:
+            X = X.to(torch.float64).contiguous()
+            if dt == "COSINE":
+                X = _normalize_rows(X)
+        rows = krows.rows(X, dt)
+        C = self.C.to(rows.device)
+        # every distance only for the detail column; otherwise no [n, k] matrix where the rows have a kernel
+        dist_all = rows.distances(C) if self.detail_col else None
+        if low:
+            # a low-precision device block of any shape: bf16-rounded centroids, as ``ops.kmeans.assign_accumulate``
             idx, d2 = kops.assign(X, C)
-            dist_all = None
-            if self.detail_col:
-                dist_all = torch.cat([pairwise_distance(X[s:s + (1 << 20)].float(), C.float(), dt).double()
-                                      for s in range(0, X.shape[0], 1 << 20)])
             best = d2.sqrt()
         else:
-            Xf = X.to(torch.float64)
-            if dt == "COSINE":
-                Xf = _normalize_rows(Xf)
-            C = self.C.to(Xf.device)
-            if not self.detail_col and C.dim() == 2 and C.shape[0] >= 1 and C.shape[1] == Xf.shape[1] and \
-                    _dense64_ok(Xf.contiguous(), C.shape[0], dt):
-                # only the id (and its distance) is asked for: no [n, k] distance matrix
-                idx, best = kd64.nearest(Xf.contiguous(), C, dt)
-                return idx, (best.sqrt_() if dt == "EUCLIDEAN" else best), None, nulls
-            dist_all = pairwise_distance(Xf, C, dt)
-            best, idx = dist_all.min(1)
-        return idx, best, dist_all, nulls
+            idx, best = rows.nearest(C, dist_all)
+        return self._outputs(idx, best, dist_all, nulls)
 
     def _outputs(self, idx, best, dist_all, nulls):
         ids = torch.as_tensor(self.model.ids, device=idx.device)[idx]

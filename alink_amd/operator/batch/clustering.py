@@ -1,6 +1,7 @@
 """Clustering batch operators (reference ``A/operator/batch/clustering/*``)."""
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -34,36 +35,25 @@ def vector_tensor(mt: MTable, col: str, device) -> torch.Tensor:
 
 def sparse_vector_matrix(mt: MTable, col: str, device, dist_type: str):
     """This rank's rows of a SPARSE vector column as a CSR ``FeatureMatrix`` when KMeans takes its sparse path
-    (``ops/kmeans_sparse.sparse_selected``: the column is a ``SparseBlock`` or holds sparse vectors, and the global
+    (``ops/kmeans_rows.sparse_selected``: the column is a ``SparseBlock`` or holds sparse vectors, and the global
     vector size exceeds what the dense kernels cover; ``ALINK_KMEANS_SPARSE`` = 1 / 0 forces / disables it), else
     None.  Every rank takes the same decision: a rank without rows follows the others."""
-    import os
-    from ...common.linalg import SparseBlock, SparseVector
-    from ...models.common.features import extract_features
-    from ...ops.kmeans_sparse import sparse_selected
+    from ...models.common.features import FeatureMatrix, extract_features
+    from ...ops.kmeans_rows import DENSE, SPARSE, column_kind, sparse_selected
     from ...parallel import comm
     if os.environ.get("ALINK_KMEANS_SPARSE", "") == "0" or dist_type.upper() not in ("EUCLIDEAN", "COSINE"):
         return None
     v = mt.col(col).values
     if isinstance(v, torch.Tensor):     # dense block: as in vector_tensor, no collective on this path
         return None
-    if isinstance(v, SparseBlock):
-        kind = 1
-    else:
-        first = next((x for x in v if x is not None), None)
-        if first is None:
-            kind = -1                   # no rows here: undecided
-        else:
-            kind = int(isinstance(first, SparseVector) or (isinstance(first, str) and ("$" in first or ":" in first)))
-    kinds = comm.all_gather_object(kind)
-    if 0 in kinds or 1 not in kinds:
+    kinds = comm.all_gather_object(column_kind(v))
+    if DENSE in kinds or SPARSE not in kinds:
         return None
     fm = extract_features(mt, None, col, device)
     flags = comm.all_gather_object((int(fm.ncols), bool(fm.is_sparse) or fm.nrows == 0))
     if not all(f[1] for f in flags) or not sparse_selected(True, max(f[0] for f in flags)):
         return None
     if not fm.is_sparse:                # a rank without rows: an empty CSR partition
-        from ...models.common.features import FeatureMatrix
         z = torch.zeros(0, dtype=torch.int64, device=device)
         fm = FeatureMatrix(crow=torch.zeros(1, dtype=torch.int64, device=device), col=z,
                            val=torch.zeros(0, dtype=torch.float64, device=device), ncols=0)

@@ -17,13 +17,11 @@ all-reduce.
   fp32 rows (``csrc/kmeans_accum.hip`` ``alink_kmeans_accum_f32``: fp64 LDS table, fixed-order fp64 reduction).
   fp64 feature matrices (VectorAssembler output) reach it through ``ALINK_KMEANS_INPUT=fp32`` (a one-time cast,
   see ``models/clustering/kmeans.train_kmeans``; ``bf16`` selects the fused bf16 kernels instead).
-* sparse rows (a CSR ``FeatureMatrix``) do not come through this module: ``ops/kmeans_sparse.py`` assigns and sums
-  them in fp64 without densifying (``csrc/kmeans_sparse.hip``; selected by ``models/clustering/kmeans.py`` and the
-  operators for sparse vector columns wider than the dense kernels cover).
-* GPU, fp64 rows of any d up to 1024 (vector columns, VectorAssembler output), any k, unweighted:
-  ``ops/kmeans_dense64.py`` (``csrc/kmeans_dense64.hip``) — fp64 MFMA scores + argmax, then per-cluster sums in a
-  fixed order without float atomics; exact fp64, ``ALINK_KMEANS_DENSE64=0`` turns it off.
+* GPU, fp64 rows of any d up to 1024, any k, unweighted: ``ops/kmeans_dense64.py``.
 * anything else: chunked PyTorch path (fp64 on CPU; on GPU fp32 GEMM of the same bf16-rounded centroids).
+
+This is the Lloyd step's ladder over dense tensors (it depends on k).  Which family serves a run's rows otherwise
+(CSR rows, the k-means|| passes, prediction) is decided once, in ``ops/kmeans_rows.py``, and described there.
 """
 from __future__ import annotations
 

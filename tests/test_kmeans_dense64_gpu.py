@@ -273,16 +273,17 @@ def test_train_matches_cpu(dist):
 
 def test_init_passes_take_kernel():
     from alink_amd import useLocalEnv
-    from alink_amd.models.clustering.kmeans import _min_dist_to, kmeans_init
+    from alink_amd.models.clustering.kmeans import kmeans_init
     from alink_amd.ops import kmeans_dense64 as kd
+    from alink_amd.ops.kmeans_rows import rows
     n, d, k = 600, 37, 4
     X, init = _blobs(n, d, k)
     Xc, Cc = torch.from_numpy(X), torch.from_numpy(init)
     Xg, Cg = Xc.cuda(), Cc.cuda()
     calls = kd.DENSE64_CALLS
-    cpu = _min_dist_to(Xc, Cc, "EUCLIDEAN")
+    cpu = rows(Xc, "EUCLIDEAN").nearest(Cc)[1]
     assert kd.DENSE64_CALLS == calls
-    gpu = _min_dist_to(Xg, Cg, "EUCLIDEAN")
+    gpu = rows(Xg, "EUCLIDEAN").nearest(Cg)[1]
     assert kd.DENSE64_CALLS == calls + 1
     # |sqrt(a) - sqrt(b)| <= sqrt|a - b| for two evaluations a, b of the squared distance to the nearest centroid
     ref, bound = _reference(Xg, Cg, "EUCLIDEAN")

@@ -9,7 +9,7 @@ Per shape ``n x d x k`` it times, with device events and after a warm-up of ever
 
 * ``assign_accumulate`` (the Lloyd step) against ``ops.kmeans.assign_accumulate_torch``;
 * ``nearest_counts`` against 2k+1 candidates (the k-means|| weights pass) and ``nearest`` distances against the
-  torch body of ``models/clustering/kmeans._min_dist_to`` for the same candidates;
+  torch kind of ``ops/kmeans_rows.py`` (chunked ``pairwise_distance``) for the same candidates;
 * ``nearest`` with the predict shape (k centroids), which has no torch counterpart worth timing: the mapper built
   the whole [n, k] matrix.
 
@@ -44,7 +44,7 @@ def timed(fn):
 
 
 def min_dist_torch(X, C, chunk=1 << 20):
-    """The torch body of ``_min_dist_to`` for fp64 rows (EUCLIDEAN)."""
+    """The minimum distance as the torch kind of ``ops/kmeans_rows.py`` computes it for fp64 rows (EUCLIDEAN)."""
     from alink_amd.models.clustering.kmeans import pairwise_distance
     return torch.cat([pairwise_distance(X[s:s + chunk], C, "EUCLIDEAN").min(1).values
                       for s in range(0, X.shape[0], chunk)])
@@ -71,6 +71,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
     from alink_amd.ops import _lib, kmeans as kops, kmeans_dense64 as kd
+    from alink_amd.ops.kmeans_rows import rows
     _lib.require()
     dev = torch.device("cuda:0")
     for shape in a.shapes.split(","):
@@ -81,6 +82,7 @@ def main():
         cand = X[pick].contiguous()
         C = cand[:k].contiguous()
         assert kd.dense64_selected(X, k)
+        R = rows(X, "EUCLIDEAN")
         state = {}
 
         def new_step():
@@ -93,7 +95,7 @@ def main():
             state["cnt"] = kd.nearest_counts(X, cand, "EUCLIDEAN")
 
         def new_dist():
-            state["nd"] = kd.nearest(X, cand, "EUCLIDEAN")[1].sqrt_()
+            state["nd"] = R.nearest(cand)[1]
 
         def old_dist():
             state["od"] = min_dist_torch(X, cand)

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Where the KMeans k-means|| initialisation spends its time (bench data: 1e8 x 128 bf16, k = 100, initSteps 2,
-the reference seeding rule).  Each helper of ``models/clustering/kmeans.py`` is wrapped with a device-synchronised
-wall timer; ``other`` is the rest of ``kmeans_init`` (threshold sums, the oversampling draw, the candidate gather).
+the reference seeding rule).  The rows object's passes (``ops/kmeans_rows.py``: ``first_cost`` and ``nearest`` are the
+minimum-distance passes, ``nearest_counts`` the weights pass) and the helpers of ``models/clustering/kmeans.py`` are
+wrapped with a device-synchronised wall timer; ``other`` is the rest of ``kmeans_init`` (threshold sums, the
+oversampling draw, the candidate gather).
 Then one full ``KMeansTrainBatchOp`` run to convergence, split into init / supersteps / the rest.
 
     python tools/kmeans_init_profile.py [--rows 100000000] [--k 100] [--reps 3]
@@ -46,12 +48,13 @@ def main():
             acc[name] = acc.get(name, 0.0) + time.perf_counter() - t
             return r
         return w
-    orig = {n: getattr(km, n) for n in ("_min_dist_to", "_nearest", "_local_kmeans", "_fetch_global_rows",
-                                        "_global_count")}
+    orig = {n: getattr(km, n) for n in ("_local_kmeans", "_fetch_global_rows", "_global_count")}
     for n, f in orig.items():
         setattr(km, n, wrap(n, f))
-    counts_orig = km.kops.nearest_counts_hip          # the candidate weights pass (one kernel, counts mode)
-    km.kops.nearest_counts_hip = wrap("nearest_counts", counts_orig)
+    kind = type(km.krows.rows(X, "EUCLIDEAN"))
+    passes = {n: getattr(kind, n) for n in ("first_cost", "nearest", "nearest_counts")}
+    for n, f in passes.items():
+        setattr(kind, n, wrap(n, f))
     res = {"rows": a.rows, "k": a.k, "initSteps": a.init_steps, "device": str(dev), "reps": []}
     for _ in range(a.reps):
         acc.clear()
@@ -67,7 +70,8 @@ def main():
         res["reps"].append(rep)
     for n, f in orig.items():
         setattr(km, n, f)
-    km.kops.nearest_counts_hip = counts_orig
+    for n, f in passes.items():
+        setattr(kind, n, f)
     # split of one full training run (the bench's convergence.reference run)
     marks = {}
     init_orig = km.kmeans_init
