@@ -44,6 +44,25 @@ class JavaRandom:
     def nextDouble(self) -> float:
         return ((self._next(26) << 27) + self._next(27)) * (1.0 / (1 << 53))
 
+    def nextDoubles(self, n: int) -> "np.ndarray":
+        """The next ``n`` values of ``nextDouble`` as a float64 array (the same draws, without a Python call each):
+        the 2 n states of the LCG by doubling — the block after m states is ``A_m s + C_m`` — in uint64, whose
+        wrap-around agrees with the generator's modulus 2^48."""
+        import numpy as np
+        n = int(n)
+        if n <= 0:
+            return np.zeros(0)
+        with np.errstate(over="ignore"):
+            a, c = np.uint64(_MULT), np.uint64(_ADD)
+            states = np.array([np.uint64(self._seed) * a + c], dtype=np.uint64)
+            while states.shape[0] < 2 * n:
+                states = np.concatenate([states, states * a + c])
+                a, c = a * a, a * c + c
+        states = states[:2 * n] & np.uint64(_MASK)
+        self._seed = int(states[-1])
+        hi, lo = states[0::2] >> np.uint64(22), states[1::2] >> np.uint64(21)       # next(26), next(27)
+        return ((hi << np.uint64(27)) + lo).astype(np.float64) * (1.0 / (1 << 53))
+
     def nextFloat(self) -> float:
         return self._next(24) / float(1 << 24)
 

@@ -10,9 +10,12 @@ middle plane ``x.(r - l) < (r + l)/2.(r - l)``; cosine: nearest child).  Cluster
 tree; leaves are numbered in BFS order and the detail vector turns tree distances into probabilities
 (``KMeansUtil.getProbArrayFromDistanceArray``).
 
-MI355X design: the samples stay on the device with an int64 tree-node id per row; an inner iteration is one
-fused projection (``X @ V`` for all dividing clusters at once), a ``where`` and one one-hot GEMM for the
-per-child segment sums, then one all-reduce of ``[#children, d + 2]`` statistics.
+MI355X design: the samples stay on the device as the rows object of ``ops/kmeans_rows.py`` (fp64 rows or CSR rows
+that are never densified, normalised once for COSINE) with an int32 tree slot per row; an inner iteration is one
+``descend`` (``ops/csrc/bisecting.hip``: every row against the plane of its own node, one pass over the rows) and
+one ``child_stats`` (the exact sort-based sums of the KMeans kernels, no float atomics), then one all-reduce of
+``[#children, d + 2]`` statistics.  Prediction is one ``descend`` launch over the whole tree.  CPU rows and the
+other row kinds keep the torch arithmetic (a projection on every dividing plane, a one-hot GEMM).
 """
 from __future__ import annotations
 
@@ -22,7 +25,7 @@ from typing import Dict, List
 import numpy as np
 import torch
 
-from ...ops.gemm import tn_matmul
+from ...ops import bisecting as bops, kmeans_rows as krows
 from ...common.javafmt import gson_dumps
 from ...common.jrandom import JavaRandom
 from ...common.linalg import DenseVector
@@ -54,24 +57,10 @@ class _Summary:
         self.clusterId, self.size, self.center, self.cost = int(cid), int(size), center, float(cost)
 
 
-def _summaries(X, node, ids: List[int], cosine: bool):
-    """Global (size, center, cost) per tree node in ``ids``."""
-    dev = X.device
-    d = X.shape[1]
-    m = len(ids)
-    pos = torch.full((int(max(ids)) + 2,), -1, dtype=torch.long, device=dev) if ids else None
-    stats = torch.zeros((m, d + 2), dtype=torch.float64, device=dev)
-    if m:
-        pos[torch.as_tensor(ids, device=dev)] = torch.arange(m, device=dev)
-        nn = node.clamp(max=pos.numel() - 1)
-        p = torch.where(node < pos.numel(), pos[nn], torch.full_like(node, -1))
-        ok = p >= 0
-        Xs, ps = X[ok], p[ok]
-        norm2 = (Xs * Xs).sum(1)
-        vec = Xs / torch.sqrt(norm2)[:, None] if cosine else Xs
-        # segment sums as one [m, n] x [n, d + 2] GEMM (few segments: atomics would serialise)
-        onehot = torch.nn.functional.one_hot(ps, m).to(X.dtype)
-        stats += tn_matmul(onehot, torch.cat([vec, torch.ones_like(norm2)[:, None], norm2[:, None]], 1))
+def _summaries(stats: torch.Tensor, ids: List[int], cosine: bool):
+    """Global (size, center, cost) per tree node in ``ids`` from this rank's ``[len(ids), d + 2]`` statistics
+    ``[sum_x | count | sum |x|^2]`` (``Rows.child_stats``)."""
+    d = stats.shape[1] - 2
     comm.all_reduce(stats, "sum")
     out = {}
     S = stats.cpu().numpy()
@@ -87,6 +76,25 @@ def _summaries(X, node, ids: List[int], cosine: bool):
     return out
 
 
+def _normalize_rows(X: torch.Tensor) -> torch.Tensor:
+    return X / torch.sqrt((X * X).sum(1, keepdim=True))
+
+
+def bisecting_rows(fm, d: int, dist: str):
+    """One rank's rows for BisectingKMeans (training and prediction): CSR where ``sparse_selected`` takes the column,
+    else a dense fp64 block under ``d`` columns; normalised once for COSINE."""
+    if fm.is_sparse and krows.sparse_selected(True, d):
+        return krows.rows(krows.sparse_rows(fm, d, dist), dist)
+    if fm.is_sparse:
+        fm.set_ncols(d)
+    X = fm.to_dense().to(torch.float64)
+    if X.shape[1] < d:
+        X = torch.nn.functional.pad(X, (0, d - X.shape[1]))
+    if dist == "COSINE":
+        X = _normalize_rows(X)
+    return krows.rows(X.contiguous(), dist)
+
+
 def train_bisecting_kmeans(mt: MTable, params: Params, env) -> List[tuple]:
     dev = env.device
     vcol = params.get("vectorCol")
@@ -98,13 +106,12 @@ def train_bisecting_kmeans(mt: MTable, params: Params, env) -> List[tuple]:
     cosine = dist == "COSINE"
     fm = extract_features(mt, None, vcol, dev)
     d = global_vector_size(fm)
-    if fm.is_sparse:
-        fm.set_ncols(d)
-    X = fm.to_dense().to(torch.float64)
-    if X.shape[1] < d:
-        X = torch.nn.functional.pad(X, (0, d - X.shape[1]))
-    node = torch.ones(X.shape[0], dtype=torch.long, device=dev)
-    summ: Dict[int, tuple] = _summaries(X, node, [1], cosine)
+    rows = bisecting_rows(fm, d, "COSINE" if cosine else "EUCLIDEAN")
+    n = rows.n
+    # a row's node is an index into ``nodes``, the list of every tree node so far (the host keeps the ids)
+    nodes: List[int] = [1]
+    node = torch.zeros(n, dtype=torch.int32, device=dev)
+    summ: Dict[int, tuple] = _summaries(rows.child_stats(node, 1, sqnorm=not cosine), [1], cosine)
     rnd = JavaRandom(0)
     while True:
         ids = set(summ)
@@ -119,36 +126,32 @@ def train_bisecting_kmeans(mt: MTable, params: Params, env) -> List[tuple]:
         for c in split:
             ctr = summ[c][1]
             level = 1.0e-4 * np.sqrt(ctr @ ctr)
-            noise = np.array([level * rnd.nextDouble() for _ in range(d)])
+            noise = level * rnd.nextDoubles(d)
             centers[2 * c], centers[2 * c + 1] = ctr - noise, ctr + noise
-        par = torch.as_tensor(split, device=dev)
-        in_div = (node[:, None] == par[None, :])
-        row_has = in_div.any(1)
-        which = in_div.float().argmax(1)
-        child = node.clone()
-        for _ in range(max_iter):
-            L = torch.as_tensor(np.stack([centers[2 * c] for c in split]), device=dev)
-            R = torch.as_tensor(np.stack([centers[2 * c + 1] for c in split]), device=dev)
-            if cosine:
-                Xn = X / torch.sqrt((X * X).sum(1, keepdim=True))
-                dl = 1.0 - (Xn @ (L / L.norm(dim=1, keepdim=True)).T)
-                dr = 1.0 - (Xn @ (R / R.norm(dim=1, keepdim=True)).T)
-                go_left = (dl < dr).gather(1, which[:, None])[:, 0]
-            else:
-                V = R - L
-                mid = 0.5 * (R + L)
-                length = (mid * V).sum(1)
-                proj = X @ V.T
-                go_left = (proj < length[None, :]).gather(1, which[:, None])[:, 0]
-            child = torch.where(row_has, torch.where(go_left, 2 * node, 2 * node + 1), node)
-            kids = [x for c in split for x in (2 * c, 2 * c + 1)]
-            s = _summaries(X, child, kids, cosine)
+        m = len(split)
+        kids = [x for c in split for x in (2 * c, 2 * c + 1)]
+        # this round's slots: the dividing nodes 0 .. m-1, then their children m .. 3m-1; every other row has -1
+        to_slot = torch.full((len(nodes),), -1, dtype=torch.int32)
+        for i, c in enumerate(split):
+            to_slot[nodes.index(c)] = i
+        start = to_slot.to(dev)[node.to(torch.int64)]
+        slot, stats = start, None
+        for it in range(max_iter):
+            table = bops.tree_table(centers, split + kids, cosine, dev)
+            slot = rows.descend(table, start.clone(), 1)
+            # sum |x|^2 only feeds the EUCLIDEAN cost, which is read after the round's last iteration
+            stats = rows.child_stats(slot - m, 2 * m, sqnorm=not cosine and it == max_iter - 1)
+            s = _summaries(stats, kids, cosine)
             for cid in kids:
                 if s[cid][0] > 0:
                     centers[cid] = s[cid][1]
-        node = child
-        kids = [x for c in split for x in (2 * c, 2 * c + 1)]
-        summ.update(_summaries(X, node, kids, cosine))
+        if max_iter < 1:
+            s = _summaries(rows.child_stats(slot - m, 2 * m, sqnorm=not cosine), kids, cosine)
+        summ.update(s)
+        # the rows that moved now sit in a child: slot m + j is node ``kids[j]``
+        first = len(nodes)
+        nodes.extend(kids)
+        node = torch.where(slot >= m, slot - m + first, node)
         if should_stop:
             break
     meta = Params().set("distanceType", dist).set("k", k).set("vectorSize", d).set("vectorCol", vcol)
@@ -176,6 +179,7 @@ class BisectingKMeansModelMapper(RichModelMapper):
             queue.extend(kids)
         self.leaf_ids = order
         self.leaf_index = {c: i for i, c in enumerate(order)}
+        self._tables = {}                   # the tree table per device, built on first use
 
     @staticmethod
     def _level(n):
@@ -237,28 +241,28 @@ class BisectingKMeansModelMapper(RichModelMapper):
             if not moved:
                 return c
 
-    def _leaves_of_device(self, X: torch.Tensor) -> torch.Tensor:
-        """``_leaves_of`` on the device (float64; the split products to rounding)."""
-        c = torch.ones(X.shape[0], dtype=torch.int64, device=X.device)
-        t = lambda a: torch.as_tensor(a, dtype=torch.float64, device=X.device)  # noqa: E731
-        while True:
-            moved = False
-            for node in torch.unique(c).tolist():
-                if not (2 * node in self.centers and 2 * node + 1 in self.centers):
-                    continue
-                rows = torch.nonzero(c == node).reshape(-1)
-                x = X[rows]
-                l, r = self.centers[2 * node], self.centers[2 * node + 1]
-                if self.cosine:
-                    xn = x / torch.sqrt((x * x).sum(1, keepdim=True))
-                    left = (1 - xn @ t(l / np.sqrt(l @ l))) < (1 - xn @ t(r / np.sqrt(r @ r)))
-                else:
-                    v, m = r - l, 0.5 * (r + l)
-                    left = x @ t(v) < float(m @ v)
-                c[rows] = torch.where(left, 2 * node, 2 * node + 1)
-                moved = True
-            if not moved:
-                return c
+    def _tree(self, dev):
+        """(tree table, leaf slot -> BFS leaf index int64 [S]) on ``dev``, built once per loaded model and device."""
+        cache, key = self._tables, str(dev)
+        if key not in cache:
+            order, queue = [], [1]
+            while queue:                    # the nodes a row can reach from the root
+                c = queue.pop(0)
+                order.append(c)
+                if 2 * c in self.centers and 2 * c + 1 in self.centers:
+                    queue.extend((2 * c, 2 * c + 1))
+            table = bops.tree_table(self.centers, order, self.cosine, dev)
+            lut = torch.tensor([self.leaf_index.get(c, -1) for c in table.nodes], dtype=torch.int64)
+            cache[key] = (table, lut.to(dev))
+        return cache[key]
+
+    def _leaves_device(self, fm) -> torch.Tensor:
+        """BFS leaf index (int64 [n], on the device) of a device column: one ``descend`` over the whole tree."""
+        dev = fm.device
+        table, lut = self._tree(dev)
+        rows = bisecting_rows(fm, self.d, "COSINE" if self.cosine else "EUCLIDEAN")
+        slot = torch.full((rows.n,), table.slot_of[1], dtype=torch.int32, device=dev)
+        return lut[rows.descend(table, slot, table.depth).to(torch.int64)]
 
     def _map_row_values(self, row):
         mt = MTable.from_rows([tuple(row)], self.dataSchema)
@@ -269,18 +273,20 @@ class BisectingKMeansModelMapper(RichModelMapper):
         vcol = self.params.get("vectorCol") if self.params.contains("vectorCol") and \
             self.params.get("vectorCol") else self.vcol
         from ..linear.model import _dev
-        dev = _dev(mt) if not self.detail_col else torch.device("cpu")
+        dev = _dev(mt)
+        v = mt.col(vcol).values
+        if not isinstance(v, torch.Tensor) and getattr(getattr(v, "val", None), "is_cuda", False):
+            dev = v.val.device                      # a sparse block on the device
+        if self.detail_col:
+            dev = torch.device("cpu")
         fm = extract_features(mt, None, vcol, dev)
+        if dev.type == "cuda":
+            if (fm.ncols > self.d) if fm.is_sparse else (fm.ncols != self.d):
+                raise RuntimeError(f"Dim of predict data not equal to vectorSize of training data: {self.d}")
+            return [Column(self._leaves_device(fm).cpu())]
         if fm.is_sparse:
             fm.set_ncols(self.d)
         X = fm.to_dense().double()
-        if dev.type == "cuda":
-            if X.shape[1] != self.d:
-                raise RuntimeError(f"Dim of predict data not equal to vectorSize of training data: {self.d}")
-            leaves = self._leaves_of_device(X)
-            ids = torch.unique(leaves)
-            idx = torch.tensor([self.leaf_index[int(i)] for i in ids.tolist()], dtype=torch.int64, device=dev)
-            return [Column(idx[torch.searchsorted(ids, leaves)].cpu())]
         X = X.numpy()
         if X.shape[1] != self.d:
             raise RuntimeError(f"Dim of predict data not equal to vectorSize of training data: {self.d}")

@@ -172,6 +172,10 @@ _SIGNATURES = {
                                      _c_vp, _c_vp, _c_int, _c_vp],
     "alink_kmeans_dense64_accum": [_c_vp, _c_int, _c_vp, _c_i64, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp,
                                    _c_vp, _c_int, _c_vp],
+    "alink_bisect_descend_f64": [_c_vp, _c_i64, _c_int, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_int,
+                                 _c_int, _c_int, _c_vp],
+    "alink_bisect_descend_csr": [_c_vp, _c_vp, _c_int, _c_vp, _c_i64, _c_i64, _c_vp, _c_int, _c_vp, _c_vp, _c_vp,
+                                 _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_vp],
 }
 
 

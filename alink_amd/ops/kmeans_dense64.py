@@ -188,17 +188,20 @@ def nearest_counts(X: torch.Tensor, C: torch.Tensor, dist_type: str, grid: int =
     return torch.bincount(nearest_torch(X, C, dist_type)[0], minlength=k)
 
 
-def _accumulate_hip(X: torch.Tensor, idx: torch.Tensor, k: int, grid: int = 0) -> torch.Tensor:
-    """[k, d+1] through the cluster-sorted row list; ``idx`` int32 / int64 [n] with every value in [0, k)."""
-    global DENSE64_CALLS
-    n, d = X.shape
-    dev = X.device
+def _sorted_work(idx: torch.Tensor, k: int, ignore_outside: bool = False):
+    """The accumulate kernel's work list for the rows' clusters ``idx`` int32 / int64 [n]: one stable sort, then
+    (perm, nchunk, wstart, wlen, cfirst, nch, cnt).  Every value must be in [0, k), unless ``ignore_outside``: such
+    rows then get the key ``k``, sort behind every cluster, and no chunk covers them (they are never read)."""
+    dev = idx.device
+    key = idx.to(torch.int32)
+    if ignore_outside:
+        key = torch.where((key >= 0) & (key < k), key, torch.full_like(key, k))
     # a stable sort keeps the rows of a cluster in ascending order; the chunk list follows from the counts alone
-    skey, perm = torch.sort(idx.to(torch.int32), stable=True)
-    cnt = torch.bincount(skey, minlength=k)
+    skey, perm = torch.sort(key, stable=True)
+    cnt = torch.bincount(skey, minlength=k + 1)[:k] if ignore_outside else torch.bincount(skey, minlength=k)
     if int(cnt.shape[0]) != k:
         raise ValueError("idx holds a cluster outside [0, k)")
-    del skey
+    del skey, key
     first = torch.cumsum(cnt, 0) - cnt                            # a cluster's first position in perm
     nch = (cnt + (ACCUM_ROWS - 1)) // ACCUM_ROWS
     cfirst = (torch.cumsum(nch, 0) - nch).contiguous()            # a cluster's first chunk
@@ -206,25 +209,47 @@ def _accumulate_hip(X: torch.Tensor, idx: torch.Tensor, k: int, grid: int = 0) -
     nchunk = int(wc.shape[0])
     wstart = first[wc] + (torch.arange(nchunk, device=dev) - cfirst[wc]) * ACCUM_ROWS
     wlen = torch.minimum(first[wc] + cnt[wc] - wstart, torch.full_like(wstart, ACCUM_ROWS)).to(torch.int32)
+    return perm, nchunk, wstart.contiguous(), wlen.contiguous(), cfirst, nch.contiguous(), cnt.contiguous()
+
+
+def _accumulate_work(X: torch.Tensor, work, k: int, grid: int = 0) -> torch.Tensor:
+    """[k, d+1] of the rows ``X`` [n, d] through a work list of ``_sorted_work`` (one list serves several ``X``)."""
+    global DENSE64_CALLS
+    n, d = X.shape
+    dev = X.device
+    perm, nchunk, wstart, wlen, cfirst, nch, cnt = work
     part = torch.empty((max(nchunk, 1), d), dtype=torch.float64, device=dev)
     buf = torch.empty((k, d + 1), dtype=torch.float64, device=dev)
-    _lib.call("alink_kmeans_dense64_accum", X.data_ptr(), d, perm.data_ptr(), nchunk, wstart.contiguous().data_ptr(),
-              wlen.contiguous().data_ptr(), k, cfirst.data_ptr(), nch.contiguous().data_ptr(),
-              cnt.contiguous().data_ptr(), part.data_ptr(), buf.data_ptr(), int(grid), _lib.stream_ptr(dev))
+    _lib.call("alink_kmeans_dense64_accum", X.data_ptr(), d, perm.data_ptr(), nchunk, wstart.data_ptr(),
+              wlen.data_ptr(), k, cfirst.data_ptr(), nch.data_ptr(), cnt.data_ptr(), part.data_ptr(), buf.data_ptr(),
+              int(grid), _lib.stream_ptr(dev))
     DENSE64_CALLS += 1
     return buf
 
 
-def accumulate(X: torch.Tensor, idx: torch.Tensor, k: int, grid: int = 0) -> torch.Tensor:
-    """[k, d+1] fp64 ``[sum_x | count]`` of the rows' clusters ``idx`` (every value in [0, k)); on the GPU the same
-    bits for every launch and every ``grid``."""
+def _accumulate_hip(X: torch.Tensor, idx: torch.Tensor, k: int, grid: int = 0,
+                    ignore_outside: bool = False) -> torch.Tensor:
+    """[k, d+1] through the cluster-sorted row list; ``idx`` int32 / int64 [n] with every value in [0, k) (or, with
+    ``ignore_outside``, the other rows left out and unread)."""
+    return _accumulate_work(X, _sorted_work(idx, k, ignore_outside), k, grid)
+
+
+def accumulate(X: torch.Tensor, idx: torch.Tensor, k: int, grid: int = 0,
+               ignore_outside: bool = False) -> torch.Tensor:
+    """[k, d+1] fp64 ``[sum_x | count]`` of the rows' clusters ``idx`` (every value in [0, k); with ``ignore_outside``
+    rows outside it add nothing and are not read on the GPU); on the GPU the same bits for every launch and every
+    ``grid``."""
     k = int(k)
     if idx.dim() != 1 or int(idx.shape[0]) != int(X.shape[0]):
         raise ValueError("idx must be an [n] tensor")
     if X.shape[0] == 0:
         return torch.zeros((k, X.shape[1] + 1), dtype=torch.float64, device=X.device)
     if _use_hip(X, k):
-        return _accumulate_hip(X, idx.to(X.device), k, grid)
+        return _accumulate_hip(X, idx.to(X.device), k, grid, ignore_outside)
+    if ignore_outside:
+        idx = idx.to(torch.int64)
+        idx = torch.where((idx >= 0) & (idx < k), idx, torch.full_like(idx, k))
+        return _accumulate_torch(X, idx, k + 1)[:k]
     return _accumulate_torch(X, idx, k)
 
 

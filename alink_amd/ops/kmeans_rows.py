@@ -15,6 +15,10 @@ and the kernel library's availability are read there:
 The Lloyd step of every tensor kind is ``ops.kmeans.assign_accumulate``, the one ladder over dense tensors: that
 choice depends on k.  With a GPU present a missing kernel library raises, unless ``ALINK_ALLOW_TORCH_FALLBACK=1``.
 Distances are FastDistance values (EUCLIDEAN: the plain distance, COSINE: ``1 - x.c``); the callers normalise.
+
+BisectingKMeans asks the same objects for its two steps: ``descend(table, slot, levels)`` compares every row with
+the split plane of its own tree node (``ops/bisecting.py``) and ``child_stats(slot, nslots)`` sums the rows per
+child.  fp64 GPU rows and CSR GPU rows take the HIP kernels; every other kind keeps the torch arithmetic.
 """
 from __future__ import annotations
 
@@ -22,7 +26,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib, kmeans as kops, kmeans_dense64 as kd64, kmeans_sparse as ksp
+from . import _lib, bisecting as bops, kmeans as kops, kmeans_dense64 as kd64, kmeans_sparse as ksp
 from .kmeans_sparse import sparse_selected  # noqa: F401  (the selection rule of sparse columns, for the callers)
 
 __all__ = ["rows", "Rows", "column_kind", "sparse_selected", "sparse_rows", "pairwise_distance"]
@@ -97,6 +101,61 @@ class Rows:
         """``launch(C, step, skip)``, which queues superstep ``step``'s fused assign kernel ahead of time, or None."""
         return None
 
+    def descend(self, table, slot: torch.Tensor, levels: int, grid: int = 0) -> torch.Tensor:
+        """The rows' tree slots (int32 [n]) after up to ``levels`` levels down ``table`` (``ops.bisecting.tree_table``)
+        from ``slot``: a row whose slot descends goes left iff its plane says so (equality and NaN go right), any
+        other row keeps its slot.  The HIP kinds move ``slot`` in place and return it.  An empty partition launches
+        nothing."""
+        if self.n == 0 or levels <= 0 or table.P == 0:
+            return slot
+        return self._descend(table, slot, int(levels), grid)
+
+    def child_stats(self, slot: torch.Tensor, nslots: int, sqnorm: bool = True, grid: int = 0) -> torch.Tensor:
+        """fp64 ``[nslots, d + 2] = [sum_x | count | sum |x|^2]`` of the rows per slot; rows whose slot is outside
+        ``[0, nslots)`` add nothing.  ``sqnorm=False`` may leave the last column zero (only the EUCLIDEAN cost reads
+        it).  An empty partition launches nothing."""
+        if self.n == 0:
+            return torch.zeros((int(nslots), self.d + 2), dtype=torch.float64, device=slot.device)
+        return self._child_stats(slot, int(nslots), sqnorm, grid)
+
+    def row_sqnorm(self) -> torch.Tensor:
+        """|x|^2 per row, fp64 [n], computed once per rows object."""
+        if getattr(self, "_sqnorm", None) is None:
+            self._sqnorm = self._row_sqnorm()
+        return self._sqnorm
+
+
+def _torch_go_left(dots, L: torch.Tensor, R: torch.Tensor, cosine: bool) -> torch.Tensor:
+    """bool [n, m]: the comparison of the torch kinds, from the children's centres L, R [m, d] and ``dots(M)`` =
+    ``X @ M.T``: exactly the expressions BisectingKMeans always evaluated."""
+    if cosine:
+        dl = 1.0 - dots(L / L.norm(dim=1, keepdim=True))
+        dr = 1.0 - dots(R / R.norm(dim=1, keepdim=True))
+        return dl < dr
+    V = R - L
+    mid = 0.5 * (R + L)
+    length = (mid * V).sum(1)
+    return dots(V) < length[None, :]
+
+
+def _torch_descend(dots, table, slot: torch.Tensor, levels: int) -> torch.Tensor:
+    """``Rows.descend`` through [n, P] products: every descending slot's plane against every row, one column kept."""
+    dev = slot.device
+    L, R = torch.as_tensor(table.lc, device=dev), torch.as_tensor(table.rc, device=dev)
+    left, right = table.left.to(torch.int64), table.right.to(torch.int64)
+    go_left = None
+    for _ in range(levels):
+        s = slot.to(torch.int64)
+        inside = (s >= 0) & (s < table.S)
+        sc = torch.where(inside, s, torch.zeros_like(s))
+        has = inside & (left[sc] >= 0)
+        which = torch.where(has, sc, torch.zeros_like(sc))      # the descending slots are 0 .. P-1
+        if go_left is None:     # the planes do not change between the levels
+            go_left = _torch_go_left(dots, L, R, table.cosine)
+        gl = go_left.gather(1, which[:, None])[:, 0]
+        slot = torch.where(has, torch.where(gl, left[sc], right[sc]), s).to(torch.int32)
+    return slot
+
 
 class _SparseRows(Rows):
     """CSR rows on ``ops/kmeans_sparse.py``."""
@@ -116,21 +175,51 @@ class _SparseRows(Rows):
     def _assign_accumulate(self, C, step):
         return ksp.assign_accumulate(self.X, C, self.dist_type)
 
-    def distances(self, C: torch.Tensor) -> torch.Tensor:
-        """[n, k] fp64 distances, in row chunks of the CSR product (the result is the only dense block)."""
+    def _dot_chunks(self, C: torch.Tensor):
+        """Yields (first row, ``X[s:e] @ C.T`` fp64 [m, k]) in row chunks of the CSR product."""
         fm, d = self.X, self.d
         col, val = ksp._clipped(fm, d)
         safe = sparse_view(fm, d, val)
         safe.col = col
         Ct = C.t().contiguous()
+        for s in range(0, fm.nrows, SPARSE_CHUNK):
+            yield s, safe[s:s + SPARSE_CHUNK].mm(Ct)
+
+    def distances(self, C: torch.Tensor) -> torch.Tensor:
+        """[n, k] fp64 distances, in row chunks of the CSR product (the result is the only dense block)."""
+        fm, d = self.X, self.d
         cn = (C * C).sum(1)[None, :]
         xn = ksp.row_sqnorm(fm, d)
         parts = []
-        for s in range(0, fm.nrows, SPARSE_CHUNK):
-            dot = safe[s:s + SPARSE_CHUNK].mm(Ct)
+        for s, dot in self._dot_chunks(C):
             parts.append(1.0 - dot if self.dist_type == "COSINE" else
                          torch.sqrt((xn[s:s + SPARSE_CHUNK, None] + cn - 2.0 * dot).abs()))
         return torch.cat(parts) if parts else torch.zeros((0, C.shape[0]), dtype=torch.float64, device=fm.device)
+
+    def _row_sqnorm(self):
+        return ksp.row_sqnorm(self.X, self.d)
+
+    def _descend(self, table, slot, levels, grid):
+        if ksp._use_hip(self.X):
+            return bops.descend_csr(self.X, table, slot, levels, grid)
+        return _torch_descend(lambda M: torch.cat([dot for _, dot in self._dot_chunks(M)]), table, slot, levels)
+
+    def _child_stats(self, slot, nslots, sqnorm, grid):
+        fm, d = self.X, self.d
+        buf = torch.zeros((nslots, d + 2), dtype=torch.float64, device=fm.device)
+        idx = torch.where((slot >= 0) & (slot < nslots), slot, torch.full_like(slot, -1)).to(torch.int32)
+        counts = torch.bincount(idx.to(torch.int64) + 1, minlength=nslots + 1)[1:]
+        if ksp._use_hip(fm):
+            buf[:, :d + 1] = ksp.accumulate_hip(fm, idx.contiguous(), nslots, d, counts, grid)
+            if sqnorm:      # the per-row norms through the dense accumulate at d = 1: no float atomics here either
+                buf[:, d + 1] = kd64.accumulate(self.row_sqnorm()[:, None], idx, nslots, grid,
+                                                ignore_outside=True)[:, 0]
+            return buf
+        key = torch.where(idx >= 0, idx, torch.full_like(idx, nslots)).to(torch.int64)      # a spare last slot
+        buf[:, :d + 1] = ksp._accumulate_torch(fm, key, nslots + 1, d)[:nslots]
+        buf[:, d + 1] = torch.zeros(nslots + 1, dtype=torch.float64, device=fm.device).index_add_(
+            0, key, self.row_sqnorm())[:nslots]
+        return buf
 
 
 def sparse_view(fm, ncols: int, val: Optional[torch.Tensor] = None):
@@ -173,6 +262,23 @@ class _TorchRows(Rows):
     def _assign_accumulate(self, C, step):
         return kops.assign_accumulate(self.X, C, reverse=kops.serpentine_reverse(step))
 
+    def _row_sqnorm(self):
+        return (self.X * self.X).sum(1)
+
+    def _descend(self, table, slot, levels, grid):
+        return _torch_descend(lambda M: self.X @ M.T, table, slot, levels)
+
+    def _child_stats(self, slot, nslots, sqnorm, grid):
+        # segment sums as one [m, n] x [n, d + 2] GEMM over the rows that have a slot
+        from .gemm import tn_matmul
+        X, d = self.X, self.d
+        ok = (slot >= 0) & (slot < nslots)
+        Xs, ps = X[ok], slot[ok].to(torch.int64)
+        norm2 = self.row_sqnorm()[ok]
+        onehot = torch.nn.functional.one_hot(ps, nslots).to(X.dtype)
+        return torch.zeros((nslots, d + 2), dtype=torch.float64, device=X.device) + tn_matmul(
+            onehot, torch.cat([Xs, torch.ones_like(norm2)[:, None], norm2[:, None]], 1))
+
     def queue_assign(self, k):
         if not kops.hip_supported(self.X, k):       # never an empty partition
             return None
@@ -209,6 +315,23 @@ class _Dense64Rows(_TorchRows):
 
     def nearest_counts(self, C):
         return kd64.nearest_counts(self.X, C, self.dist_type)
+
+    def _descend(self, table, slot, levels, grid):
+        if kd64._use_hip(self.X, 1):
+            return bops.descend_f64(self.X, table, slot, levels, grid)
+        return super()._descend(table, slot, levels, grid)
+
+    def _child_stats(self, slot, nslots, sqnorm, grid):
+        if not kd64._use_hip(self.X, nslots):
+            return super()._child_stats(slot, nslots, sqnorm, grid)
+        # one stable sort of the slots serves both accumulates; rows without a slot sort last and are not read
+        X, d = self.X, self.d
+        work = kd64._sorted_work(slot, nslots, ignore_outside=True)
+        buf = torch.zeros((nslots, d + 2), dtype=torch.float64, device=X.device)
+        buf[:, :d + 1] = kd64._accumulate_work(X, work, nslots, grid)
+        if sqnorm:
+            buf[:, d + 1] = kd64._accumulate_work(self.row_sqnorm()[:, None], work, nslots, grid)[:, 0]
+        return buf
 
 
 def rows(X, dist_type: str) -> Rows:

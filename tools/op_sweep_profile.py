@@ -285,6 +285,8 @@ def main():
             "kmeans_predict_detail": lambda: A.KMeansPredictBatchOp().setPredictionCol("p")
             .setPredictionDetailCol("d").setReservedCols([]).linkFrom(km_model, vsrc).getOutputTable()
             .col("p").values,
+            "bisecting_kmeans_train": lambda: A.BisectingKMeansTrainBatchOp().setVectorCol("vec").setK(8).setMaxIter(3)
+            .linkFrom(vsrc).getOutputTable(),
             "bisecting_kmeans_predict": lambda: A.BisectingKMeansPredictBatchOp().setPredictionCol("p")
             .setReservedCols([]).linkFrom(bkm, vsrc).getOutputTable().col("p").values,
             "select_expr": lambda: A.SelectBatchOp().setClause("x0 * 2 + x1 AS a, label").linkFrom(src)
