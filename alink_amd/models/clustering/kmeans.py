@@ -432,7 +432,7 @@ class KMeansUpdateCentroids(ComputeFunction):
         buf = ctx.getObj(CENTROID_ALL_REDUCE)
         prev = old[1] if old is not None and old[1] is not None else None
         if self.dist_type == "EUCLIDEAN" and ctx.getObj(TRAIN_DATA).fused_update and kops.update_supported(buf) \
-                and (_lib.available() or not _lib.torch_fallback_allowed()):
+                and _lib.kernels_enabled():
             C, shift, has_empty = self._fused_update(ctx, buf, prev)
             weights = buf[:, -1]
             if has_empty:

@@ -825,7 +825,7 @@ def feature_device() -> torch.device:
     from ...common.mlenv import MLEnvironmentFactory
     from ...ops import _lib
     dev = MLEnvironmentFactory.getDefault().device
-    if dev.type == "cuda" and (_lib.available() or not _lib.torch_fallback_allowed()):
+    if dev.type == "cuda" and _lib.kernels_enabled():
         return dev
     return torch.device("cpu")
 

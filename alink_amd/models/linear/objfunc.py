@@ -312,8 +312,7 @@ class UnaryLossObjFunc(OptimObjFunc):
         from ...ops import _lib, linear as lops
         X = data.X.dense
         code = lops.loss_code(self.unary)
-        if code is not None and lops.hip_linear_supported(X) and (_lib.available()
-                                                                  or not _lib.torch_fallback_allowed()):
+        if code is not None and lops.hip_linear_supported(X) and _lib.kernels_enabled():
             return lops.linear_grad_hip(X, data.y, data.w, coef, code[0], code[1])[0]   # one pass over X
         if code is not None and lops.hip_sparse_supported(data.X):
             return lops.sparse_grad_hip(data.X, data.y, data.w, coef, code[0], code[1])[0]   # CSR + CSC kernels
@@ -331,7 +330,7 @@ class UnaryLossObjFunc(OptimObjFunc):
         X = data.X.dense
         code = lops.loss_code(self.unary)
         if code is not None and lops.hip_linear_supported(X) and num_step + 1 <= lops.SEARCH_MAX_STEPS and \
-                (_lib.available() or not _lib.torch_fallback_allowed()) and not lops.k14_disabled():
+                not lops.k14_disabled() and _lib.kernels_enabled():
             # K14: both margins and all num_step+1 losses in one pass over X
             return lops.search_losses_hip(X, data.y, data.w, coef, dirv, code[0], code[1], beta, num_step + 1)
         E = data.X.mm(torch.stack([coef, dirv], 1))  # one pass over X for both margins

@@ -60,11 +60,6 @@ def numeric_column(mt: MTable, c: str, device) -> (torch.Tensor, torch.Tensor):
     return torch.where(null, torch.zeros_like(v), v), null
 
 
-def _gpu_quantize_ok() -> bool:
-    from ...ops import _lib
-    return _lib.available() or not _lib.torch_fallback_allowed()
-
-
 def _raw_column(mt: MTable, c: str, device):
     """Numeric column in its own float dtype on ``device`` (null mask or None) — the quantize kernel reads it
     in place."""
@@ -176,7 +171,8 @@ def build_bins(mt: MTable, feature_cols: Sequence[str], cat_cols: Sequence[str],
     sample_idx = _sample_rows(n, cap, seed) if cont else np.zeros(0, dtype=np.int64)
     thresholds: List[Optional[np.ndarray]] = [None] * F
     bin_values: List[Optional[np.ndarray]] = [None] * F
-    gpu = torch.device(device).type == "cuda" and _gpu_quantize_ok()
+    from ...ops import _lib
+    gpu = torch.device(device).type == "cuda" and bool(cont) and _lib.kernels_enabled()
     cols_dev = {}
     if cont:
         sidx = torch.as_tensor(sample_idx, device=device)

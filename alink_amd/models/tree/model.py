@@ -462,7 +462,7 @@ class _DeviceForest:
         if use_kernel is None:
             use_kernel = torch.device(self.dev).type == "cuda" and _lib.available()
         if use_kernel:
-            L = _lib.require()
+            _lib.require()
             out = torch.empty((n, self.stride // self.code_bytes), dtype=ct, device=self.dev)
             # column pointers go up from pinned memory without a host wait (a pageable copy would block until the
             # previous chunk's kernels finish)
@@ -474,11 +474,9 @@ class _DeviceForest:
                 if v.dtype != torch.float64 or not v.is_contiguous() or v.device != torch.device(self.dev) or \
                         v.numel() < row0 + n:
                     raise ValueError("tree codes need contiguous fp64 device columns covering the rows")
-            rc = L.alink_tree_codes(ptrs.data_ptr(), len(self.cont), self.cont_slots.data_ptr(), self.TW.data_ptr(),
-                                    self.W, int(row0), int(n), self.stride, self.code_bytes, out.data_ptr(),
-                                    _lib.stream_ptr(self.dev))
-            if rc != 0:
-                raise RuntimeError(f"alink_tree_codes failed: {rc}")
+            _lib.call("alink_tree_codes", ptrs.data_ptr(), len(self.cont), self.cont_slots.data_ptr(),
+                      self.TW.data_ptr(), self.W, int(row0), int(n), self.stride, self.code_bytes, out.data_ptr(),
+                      _lib.stream_ptr(self.dev))
             for f in self.slot:
                 if f in self.cat_features:
                     v = cat_codes[f][row0:row0 + n]
@@ -596,16 +594,16 @@ class TreeModelMapper(RichModelMapper):
 
     def _accumulate_device(self, mt, flat: "_FlatForest", dev):
         """(acc, wacc) on the GPU (``ops/csrc/tree_predict.hip``), or None when the forest does not fit the kernel
-        (code width / stack) — the caller then takes the host walk."""
+        (code width / stack) or the torch fall-back stands in for a missing library — the caller then takes the
+        host walk."""
         from ...ops import _lib
         dfo = getattr(self, "_dforest", None)
         if dfo is None or dfo.dev != dev:
             sizes = [len(self.cat_maps.get(c, {})) if c in self.cat_cols else 0 for c in self.feature_cols]
             cat_idx = [j for j, c in enumerate(self.feature_cols) if c in self.cat_cols]
             dfo = self._dforest = _DeviceForest(flat, cat_idx, sizes, dev)
-        if not dfo.supported:
+        if not dfo.supported or not _lib.kernels_enabled():
             return None
-        L = _lib.require()
         n = mt.num_rows
         cols = {f: self._cont_column(mt, self.feature_cols[f], dev) for f in dfo.cont}
         cats = {f: self._cat_column(mt, self.feature_cols[f], dev) for f in dfo.slot if f in dfo.cat_features}
@@ -618,13 +616,10 @@ class TreeModelMapper(RichModelMapper):
         for lo in range(0, n, chunk):
             hi = min(n, lo + chunk)
             codes = dfo.codes(cols, cats, hi - lo, row0=lo)
-            rc = L.alink_tree_predict(codes.data_ptr(), hi - lo, dfo.stride, dfo.code_bytes, dfo.nodes.data_ptr(),
-                                      dfo.dist.data_ptr(), dfo.nd, dfo.wsum.data_ptr(), dfo.cat.data_ptr(),
-                                      int(dfo.cat.shape[1]), dfo.roots.data_ptr(), int(dfo.roots.numel()),
-                                      acc[lo:hi].data_ptr(), wacc[lo:hi].data_ptr(), err.data_ptr(),
-                                      _lib.stream_ptr(dev))
-            if rc != 0:
-                raise RuntimeError(f"alink_tree_predict failed: {rc}")
+            _lib.call("alink_tree_predict", codes.data_ptr(), hi - lo, dfo.stride, dfo.code_bytes, dfo.nodes.data_ptr(),
+                      dfo.dist.data_ptr(), dfo.nd, dfo.wsum.data_ptr(), dfo.cat.data_ptr(), int(dfo.cat.shape[1]),
+                      dfo.roots.data_ptr(), int(dfo.roots.numel()), acc[lo:hi].data_ptr(), wacc[lo:hi].data_ptr(),
+                      err.data_ptr(), _lib.stream_ptr(dev))
         e = int(err.item())
         if e & 1:
             raise RuntimeError("Model is broken. Sum weight is zero.")
@@ -699,9 +694,7 @@ class TreeModelMapper(RichModelMapper):
         res = None
         dev = self._device(mt) if mt.num_rows and len(flat.roots) else None
         if dev is not None:
-            from ...ops import _lib
-            if _lib.available() or not _lib.torch_fallback_allowed():
-                res = self._accumulate_device(mt, flat, dev)
+            res = self._accumulate_device(mt, flat, dev)
         if res is None:
             res = self._accumulate(self._features(mt), flat)
         preds, details = self._finish(*res)

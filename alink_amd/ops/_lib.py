@@ -15,7 +15,7 @@ from typing import Optional
 
 import torch  # noqa: F401  (loads torch's HIP runtime first; our .so resolves libamdhip64.so.7 to it)
 
-__all__ = ["lib", "require", "available", "call", "LIB_PATH", "stream_ptr"]
+__all__ = ["lib", "require", "available", "kernels_enabled", "call", "query", "LIB_PATH", "stream_ptr"]
 
 LIB_PATH = os.environ.get("ALINK_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libalink_hip.so")
 _lib: Optional[ctypes.CDLL] = None
@@ -50,9 +50,11 @@ def _load():
         return None
     # every entry point is a ``kernel`` span on the timeline when utils.trace is on (host launch cost + device
     # time from HIP events on the caller's stream); one flag check per call otherwise
+    # (not the value queries and host-side allocations; alink_oneshot_allreduce has its own span in parallel/oneshot.py)
     from ..utils import trace
     for name in _SIGNATURES:
-        if not name.endswith(("_grid", "_pad", "_padded_rank", "_kmax", "_alloc", "_free")):
+        if not (name.endswith(("_grid", "_pad", "_padded_rank", "_kmax", "_alloc", "_free"))
+                or name.startswith("alink_ar_") or name == "alink_oneshot_allreduce"):
             setattr(L, name, trace.traced_call(getattr(L, name), name[len("alink_"):]))
     _lib = L
     return _lib
@@ -176,6 +178,16 @@ _SIGNATURES = {
                                  _c_int, _c_int, _c_vp],
     "alink_bisect_descend_csr": [_c_vp, _c_vp, _c_int, _c_vp, _c_i64, _c_i64, _c_vp, _c_int, _c_vp, _c_vp, _c_vp,
                                  _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_vp],
+    "alink_ar_alloc": [_c_i64, ctypes.POINTER(_c_vp)],
+    "alink_ar_free": [_c_vp],
+    "alink_ar_ipc_handle": [_c_vp, _c_vp],
+    "alink_ar_ipc_open": [_c_vp, ctypes.POINTER(_c_vp)],
+    "alink_ar_ipc_close": [_c_vp],
+    "alink_ar_handle_size": [],
+    "alink_ar_host_word_alloc": [ctypes.POINTER(_c_vp), ctypes.POINTER(_c_vp)],
+    "alink_ar_host_word_free": [_c_vp],
+    "alink_oneshot_allreduce": [_c_vp, _c_vp, _c_i64, _c_int, _c_int, _c_int, _c_int, ctypes.c_uint32, _c_vp, _c_vp,
+                                _c_i64, _c_int, _c_int, _c_d, _c_vp, _c_vp, _c_vp],
 }
 
 
@@ -194,15 +206,33 @@ def require() -> ctypes.CDLL:
     return L
 
 
-def call(name: str, *args) -> None:
-    """Call entry point ``name``; a non-zero return code raises."""
+def call(name: str, *args, accept=()) -> int:
+    """Call entry point ``name``; a non-zero return code raises, except the codes listed in ``accept``, which
+    are returned for the caller to act on."""
     rc = getattr(require(), name)(*args)
-    if rc != 0:
+    if rc != 0 and rc not in accept:
         raise RuntimeError(f"{name} failed: {rc}")
+    return rc
 
 
-def torch_fallback_allowed() -> bool:
-    return os.environ.get("ALINK_ALLOW_TORCH_FALLBACK", "0") == "1"
+def query(name: str, *args) -> int:
+    """The plain int of an entry point that returns a value (``*_grid``, ``*_pad``, ``*_kmax``, ...), or of a
+    host-side alloc / free whose status the caller judges itself.  Never raises on the value."""
+    return int(getattr(require(), name)(*args))
+
+
+def kernels_enabled() -> bool:
+    """The fall-back rule, asked once a shape check has said that the HIP path applies: True when the library
+    loaded, False when it did not and ``ALINK_ALLOW_TORCH_FALLBACK=1``, else the ``require()`` error.
+
+    Known exceptions, which test bare ``available()`` and take torch quietly without the library (kept as they
+    are): ``kmeans.local_lloyd_ok``, ``tree.fm_eligible``, ``kmeans_sparse.row_sqnorm``, the ``seed_ref_hip`` /
+    ``par_pick_hip`` gates in ``models/clustering/kmeans.py`` and the ``alink_tree_codes`` gate in
+    ``models/tree/model.py``."""
+    if _load() is None and os.environ.get("ALINK_ALLOW_TORCH_FALLBACK", "0") == "1":
+        return False
+    require()       # raises: no quiet fall-back on a GPU
+    return True
 
 
 def stream_ptr(device=None) -> int:

@@ -53,10 +53,9 @@ def normal_equations_torch(indptr, nbr, rating, Y, implicit: bool, alpha: float)
 def normal_equations(indptr: torch.Tensor, nbr: torch.Tensor, rating: torch.Tensor, Y: torch.Tensor,
                      implicit: bool = False, alpha: float = 0.0):
     r = Y.shape[1]
-    if not Y.is_cuda or r > 64 or (not _lib.available() and _lib.torch_fallback_allowed()):
+    if not Y.is_cuda or r > 64 or not _lib.kernels_enabled():
         return normal_equations_torch(indptr, nbr, rating, Y, implicit, alpha)
-    L = _lib.require()
-    m = indptr.numel() - 1
+    m =indptr.numel() - 1
     indptr = indptr.to(torch.int64).contiguous()
     nbr = nbr.to(torch.int32).contiguous()
     rating = rating.to(torch.float32).contiguous()
@@ -65,11 +64,8 @@ def normal_equations(indptr: torch.Tensor, nbr: torch.Tensor, rating: torch.Tens
     b = torch.empty((m, r), dtype=torch.float32, device=Y.device)
     if m == 0:
         return A, b
-    rc = L.alink_als_gram_f32(indptr.data_ptr(), nbr.data_ptr(), rating.data_ptr(), Yf.data_ptr(), m, r,
-                              int(bool(implicit)), float(alpha), A.data_ptr(), b.data_ptr(),
-                              _lib.stream_ptr(Y.device))
-    if rc != 0:
-        raise RuntimeError(f"alink_als_gram_f32 failed: {rc}")
+    _lib.call("alink_als_gram_f32", indptr.data_ptr(), nbr.data_ptr(), rating.data_ptr(), Yf.data_ptr(), m, r,
+              int(bool(implicit)), float(alpha), A.data_ptr(), b.data_ptr(), _lib.stream_ptr(Y.device))
     return A, b
 
 
@@ -134,7 +130,7 @@ WOODBURY_BUCKETS = tuple(int(x) for x in __import__("os").environ.get("ALINK_ALS
 
 
 def fused_supported(Y: torch.Tensor) -> bool:
-    return Y.is_cuda and Y.shape[1] <= 64 and (_lib.available() or not _lib.torch_fallback_allowed())
+    return Y.is_cuda and Y.shape[1] <= 64 and _lib.kernels_enabled()
 
 
 _PLANS = {}
@@ -183,7 +179,7 @@ def _row_plan(indptr: torch.Tensor, nbr: torch.Tensor, n_factors: int, buckets: 
 def fused_solve(indptr: torch.Tensor, nbr: torch.Tensor, rating: torch.Tensor, Y: torch.Tensor, reg: torch.Tensor,
                 implicit: bool = False, alpha: float = 0.0, YtY: torch.Tensor = None) -> torch.Tensor:
     """x_u (float32 [m, r]) of ``(sum c y y^T + reg_u I [+ YtY]) x = sum w y`` for every CSR row u (GPU)."""
-    L = _lib.require()
+    _lib.require()
     m = indptr.numel() - 1
     r = Y.shape[1]
     dev = Y.device
@@ -198,44 +194,37 @@ def fused_solve(indptr: torch.Tensor, nbr: torch.Tensor, rating: torch.Tensor, Y
     yty = None if YtY is None else YtY.to(device=dev, dtype=torch.float64).contiguous()
     status = torch.zeros(m, dtype=torch.int32, device=dev)
     st = _lib.stream_ptr(dev)
-    RP = int(L.alink_als_padded_rank(r))
+    RP = _lib.query("alink_als_padded_rank", r)
     buckets = [P for P in WOODBURY_BUCKETS if WOODBURY and not implicit and yty is None and P < RP]
     plan = _row_plan(indptr, nbr, Yf.shape[0], tuple(buckets))
     heavy, light = plan["heavy"], plan["light"]
     for P, ids in zip(buckets, plan["buckets"]):
         if ids.numel():
             if P == 16 and WOODBURY_MFMA:
-                rc = L.alink_als_woodbury16_mfma(indptr.data_ptr(), nbr.data_ptr(), rating.data_ptr(), Yf.data_ptr(),
-                                                 ids.numel(), r, regd.data_ptr(), ids.data_ptr(), X.data_ptr(),
-                                                 status.data_ptr(), st)
+                _lib.call("alink_als_woodbury16_mfma", indptr.data_ptr(), nbr.data_ptr(), rating.data_ptr(),
+                          Yf.data_ptr(), ids.numel(), r, regd.data_ptr(), ids.data_ptr(), X.data_ptr(),
+                          status.data_ptr(), st)
             else:
-                rc = L.alink_als_woodbury_solve(indptr.data_ptr(), nbr.data_ptr(), rating.data_ptr(), Yf.data_ptr(),
-                                                ids.numel(), r, regd.data_ptr(), ids.data_ptr(), P, X.data_ptr(),
-                                                status.data_ptr(), st)
-            if rc != 0:
-                raise RuntimeError(f"alink_als_woodbury_solve failed: {rc}")
+                _lib.call("alink_als_woodbury_solve", indptr.data_ptr(), nbr.data_ptr(), rating.data_ptr(),
+                          Yf.data_ptr(), ids.numel(), r, regd.data_ptr(), ids.data_ptr(), P, X.data_ptr(),
+                          status.data_ptr(), st)
     nl = m if light is None else light.numel()
     if nl:
-        fn = L.alink_als_mfma_solve if (MFMA_LIGHT and RP == 64) else L.alink_als_fused_solve
-        rc = fn(indptr.data_ptr(), nbr.data_ptr(), rating.data_ptr(), Yf.data_ptr(), nl, r, int(bool(implicit)),
-                float(alpha), regd.data_ptr(), None if yty is None else yty.data_ptr(),
-                None if light is None else light.data_ptr(), X.data_ptr(), status.data_ptr(), st)
-        if rc != 0:
-            raise RuntimeError(f"{fn.__name__} failed: {rc}")
+        _lib.call("alink_als_mfma_solve" if (MFMA_LIGHT and RP == 64) else "alink_als_fused_solve",
+                  indptr.data_ptr(), nbr.data_ptr(), rating.data_ptr(), Yf.data_ptr(), nl, r, int(bool(implicit)),
+                  float(alpha), regd.data_ptr(), None if yty is None else yty.data_ptr(),
+                  None if light is None else light.data_ptr(), X.data_ptr(), status.data_ptr(), st)
     if heavy.numel():
         # popular items: the neighbour list is split into HEAVY_CHUNK pieces, one wave each (partial Grams
         # summed in fp64), then one wave per row solves
         chunk_row, chunk_start = plan["chunk_row"], plan["chunk_start"]
         G = torch.zeros((heavy.numel(), RP, RP), dtype=torch.float64, device=dev)
         B = torch.zeros((heavy.numel(), RP), dtype=torch.float64, device=dev)
-        rc = L.alink_als_heavy_solve(indptr.data_ptr(), nbr.data_ptr(), rating.data_ptr(), Yf.data_ptr(), r,
-                                     int(bool(implicit)), float(alpha), regd.data_ptr(),
-                                     None if yty is None else yty.data_ptr(), heavy.data_ptr(), heavy.numel(),
-                                     chunk_row.contiguous().data_ptr(), chunk_start.contiguous().data_ptr(),
-                                     chunk_row.numel(), HEAVY_CHUNK, G.data_ptr(), B.data_ptr(), X.data_ptr(),
-                                     status.data_ptr(), HEAVY_MFMA, st)
-        if rc != 0:
-            raise RuntimeError(f"alink_als_heavy_solve failed: {rc}")
+        _lib.call("alink_als_heavy_solve", indptr.data_ptr(), nbr.data_ptr(), rating.data_ptr(), Yf.data_ptr(), r,
+                  int(bool(implicit)), float(alpha), regd.data_ptr(), None if yty is None else yty.data_ptr(),
+                  heavy.data_ptr(), heavy.numel(), chunk_row.contiguous().data_ptr(),
+                  chunk_start.contiguous().data_ptr(), chunk_row.numel(), HEAVY_CHUNK, G.data_ptr(), B.data_ptr(),
+                  X.data_ptr(), status.data_ptr(), HEAVY_MFMA, st)
     bad = torch.nonzero(status != 0, as_tuple=False).reshape(-1)
     if bad.numel():                         # singular / indefinite rows: pinv like the chunked solver
         starts, ends = indptr[:-1][bad], indptr[1:][bad]

@@ -28,12 +28,7 @@ MODES = {"standard": 0, "minmax": 1, "maxabs": 2, "impute": 3, "binarize": 4}
 
 
 def _use_kernel(t: torch.Tensor) -> bool:
-    return t.is_cuda and (_lib.available() or not _lib.torch_fallback_allowed())
-
-
-def _check(rc: int, name: str) -> None:
-    if rc != 0:
-        raise RuntimeError(f"{name} failed: {rc}")
+    return t.is_cuda and _lib.kernels_enabled()
 
 
 # ---------------------------------------------------------------------------------------------------- K6
@@ -53,7 +48,6 @@ def gbdt_grad_stats_torch(pred: torch.Tensor, y: torch.Tensor, w: Optional[torch
 def gbdt_grad_stats(pred: torch.Tensor, y: torch.Tensor, w: Optional[torch.Tensor], algo: int) -> torch.Tensor:
     if not _use_kernel(pred):
         return gbdt_grad_stats_torch(pred, y, w, algo)
-    L = _lib.require()
     n = pred.numel()
     assert pred.dtype == y.dtype == torch.float32 and y.numel() == n and (w is None or w.numel() == n)
     pred, y = pred.contiguous(), y.contiguous()
@@ -61,8 +55,8 @@ def gbdt_grad_stats(pred: torch.Tensor, y: torch.Tensor, w: Optional[torch.Tenso
         assert w.dtype == torch.float32
         w = w.contiguous()
     out = torch.empty((n, 4), dtype=torch.float32, device=pred.device)
-    _check(L.alink_gbdt_grad_stats(pred.data_ptr(), y.data_ptr(), w.data_ptr() if w is not None else None, n,
-                                   int(algo), out.data_ptr(), _lib.stream_ptr(pred.device)), "alink_gbdt_grad_stats")
+    _lib.call("alink_gbdt_grad_stats", pred.data_ptr(), y.data_ptr(), w.data_ptr() if w is not None else None, n,
+              int(algo), out.data_ptr(), _lib.stream_ptr(pred.device))
     return out
 
 
@@ -90,7 +84,6 @@ def gbdt_rank_stats(pred: torch.Tensor, gain: torch.Tensor, w: Optional[torch.Te
     if sizes.numel() and int(sizes.max()) > RANK_MAX_POSITION:
         raise ValueError(f"a query has more than {RANK_MAX_POSITION} rows (the reference's kMaxPosition)")
     if _use_kernel(pred):
-        L = _lib.require()
         pred, gain = pred.contiguous(), gain.contiguous()
         off = offsets.to(device=pred.device, dtype=torch.int64).contiguous()
         if w is not None:
@@ -98,10 +91,9 @@ def gbdt_rank_stats(pred: torch.Tensor, gain: torch.Tensor, w: Optional[torch.Te
         out = torch.empty((n, 4), dtype=torch.float32, device=pred.device)
         rs = torch.empty(n, dtype=torch.int32, device=pred.device)
         ss = torch.empty(n, dtype=torch.float32, device=pred.device)
-        _check(L.alink_gbdt_rank_stats(pred.data_ptr(), gain.data_ptr(), None if w is None else w.data_ptr(),
-                                       off.data_ptr(), off.numel() - 1, dcg_discount(pred.device).data_ptr(),
-                                       int(algo), rs.data_ptr(), ss.data_ptr(), out.data_ptr(),
-                                       _lib.stream_ptr(pred.device)), "alink_gbdt_rank_stats")
+        _lib.call("alink_gbdt_rank_stats", pred.data_ptr(), gain.data_ptr(), None if w is None else w.data_ptr(),
+                  off.data_ptr(), off.numel() - 1, dcg_discount(pred.device).data_ptr(), int(algo), rs.data_ptr(),
+                  ss.data_ptr(), out.data_ptr(), _lib.stream_ptr(pred.device))
         return out
     from .. import _native
     res = _native.gbdt_rank_grad(pred.detach().cpu().numpy(), gain.detach().cpu().numpy(),
@@ -124,13 +116,12 @@ def gbdt_leaf_update(pred: torch.Tensor, codes: torch.Tensor, vals: torch.Tensor
     """Returns the updated prediction (in place on the GPU path)."""
     if not _use_kernel(pred):
         return gbdt_leaf_update_torch(pred, codes, vals)
-    L = _lib.require()
     assert pred.dtype == torch.float32 and pred.is_contiguous() and codes.dtype == torch.int32
     assert codes.numel() == pred.numel() and vals.numel() >= 1
     codes = codes.contiguous()
     vals = vals.to(device=pred.device, dtype=torch.float64).contiguous()
-    _check(L.alink_gbdt_leaf_update(pred.data_ptr(), codes.data_ptr(), vals.data_ptr(), vals.numel(), pred.numel(),
-                                    _lib.stream_ptr(pred.device)), "alink_gbdt_leaf_update")
+    _lib.call("alink_gbdt_leaf_update", pred.data_ptr(), codes.data_ptr(), vals.data_ptr(), vals.numel(),
+              pred.numel(), _lib.stream_ptr(pred.device))
     return pred
 
 
@@ -159,7 +150,6 @@ def col_transform(X: torch.Tensor, mode: str, a: Optional[torch.Tensor] = None, 
     """``X`` [n, d] or [n] fp32/fp64; ``a``/``b`` fp64 per-column parameters of length d (see module doc)."""
     if not _use_kernel(X) or X.dtype not in (torch.float32, torch.float64):
         return col_transform_torch(X, mode, a, b, lo, hi)
-    L = _lib.require()
     X = X.contiguous()
     d = X.shape[1] if X.dim() == 2 else 1
     n = X.shape[0]
@@ -174,7 +164,6 @@ def col_transform(X: torch.Tensor, mode: str, a: Optional[torch.Tensor] = None, 
 
     pa, pb = prm(a), prm(b)
     out = torch.empty(X.shape, dtype=torch.float64, device=dev)
-    _check(L.alink_col_transform(X.data_ptr(), n, d, 0 if X.dtype == torch.float32 else 1, MODES[mode],
-                                 pa.data_ptr(), pb.data_ptr(), float(lo), float(hi), out.data_ptr(),
-                                 _lib.stream_ptr(dev)), "alink_col_transform")
+    _lib.call("alink_col_transform", X.data_ptr(), n, d, 0 if X.dtype == torch.float32 else 1, MODES[mode],
+              pa.data_ptr(), pb.data_ptr(), float(lo), float(hi), out.data_ptr(), _lib.stream_ptr(dev))
     return out

@@ -67,27 +67,23 @@ def csr_assemble(idx: torch.Tensor, val: Optional[torch.Tensor], valid: Optional
     m, n = idx.shape
     dev = idx.device
     if dev.type == "cuda" and 1 <= m <= 64:
-        L = _lib.require()
+        _lib.require()
         ii = idx.to(torch.int32).contiguous()
         vv = None if val is None else val.to(torch.float64).contiguous()
         ok = None if valid is None else valid.to(torch.uint8).contiguous()
         cnt = torch.empty(n, dtype=torch.int64, device=dev)
         st = _lib.stream_ptr(dev)
-        rc = L.alink_csr_assemble(n, m, ii.data_ptr(), None, None if ok is None else ok.data_ptr(), cnt.data_ptr(),
-                                  None, None, None, st)
-        if rc != 0:
-            raise RuntimeError(f"alink_csr_assemble (count) failed: {rc}")
+        _lib.call("alink_csr_assemble", n, m, ii.data_ptr(), None, None if ok is None else ok.data_ptr(),
+                  cnt.data_ptr(), None, None, None, st)        # count
         crow = torch.zeros(n + 1, dtype=torch.int64, device=dev)
         torch.cumsum(cnt, 0, out=crow[1:])
         nnz = int(crow[-1]) if n else 0
         col = torch.empty(nnz, dtype=torch.int32, device=dev)
         out = torch.empty(nnz, dtype=torch.float64, device=dev)
         if nnz:
-            rc = L.alink_csr_assemble(n, m, ii.data_ptr(), None if vv is None else vv.data_ptr(),
-                                      None if ok is None else ok.data_ptr(), cnt.data_ptr(), crow.data_ptr(),
-                                      col.data_ptr(), out.data_ptr(), st)
-            if rc != 0:
-                raise RuntimeError(f"alink_csr_assemble (write) failed: {rc}")
+            _lib.call("alink_csr_assemble", n, m, ii.data_ptr(), None if vv is None else vv.data_ptr(),
+                      None if ok is None else ok.data_ptr(), cnt.data_ptr(), crow.data_ptr(), col.data_ptr(),
+                      out.data_ptr(), st)                       # write
         return SparseBlock(crow, col, out, size, dense_ratio)
     # host / fallback: sort (row, index) keys, merge duplicates with index_add
     rows = torch.arange(n, device=dev, dtype=torch.int64).repeat(m)
@@ -154,7 +150,7 @@ def vector_assemble(parts, n: int, skip: Optional[torch.Tensor] = None, dense_ra
     col = torch.empty(nnz, dtype=torch.int32, device=dev)
     val = torch.empty(nnz, dtype=torch.float64, device=dev)
     if dev.type == "cuda" and n and nnz and use_kernel:
-        L = _lib.require()
+        _lib.require()
         sk = None if skip is None else skip.to(dev).to(torch.uint8).contiguous()
         desc = torch.zeros((len(norm), 8), dtype=torch.int64)
         pos = 0
@@ -178,11 +174,9 @@ def vector_assemble(parts, n: int, skip: Optional[torch.Tensor] = None, dense_ra
         ddesc = desc.to(dev)
         tot = crow[1:] - crow[:-1]
         variant = 2 if len(norm) <= 16 and int(tot.max()) < (1 << 22) else 1
-        rc = L.alink_vector_assemble(n, len(norm), ddesc.data_ptr(), crow.data_ptr(), col.data_ptr(), val.data_ptr(),
-                                     VA_VARIANT if VA_VARIANT in (1, 2) and variant == 2 else variant,
-                                     _lib.stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError(f"alink_vector_assemble failed: {rc}")
+        _lib.call("alink_vector_assemble", n, len(norm), ddesc.data_ptr(), crow.data_ptr(), col.data_ptr(),
+                  val.data_ptr(), VA_VARIANT if VA_VARIANT in (1, 2) and variant == 2 else variant,
+                  _lib.stream_ptr(dev))
         torch.cuda.current_stream(dev).synchronize()      # the descriptor's raw pointers must outlive the kernel
         _KEEP.clear()
     elif nnz:
@@ -217,7 +211,7 @@ def _keep(t):
 def csr_mv(crow: torch.Tensor, col: torch.Tensor, val: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
     """``out[r] = sum_k val[k] * v[col[k]]`` for the CSR rows (fp64) on the GPU (``alink_csr_mv_f64``)."""
     global CSR_MV_CALLS
-    L = _lib.require()
+    _lib.require()
     dev = val.device
     n = int(crow.numel()) - 1
     out = torch.empty(n, dtype=torch.float64, device=dev)
@@ -228,9 +222,7 @@ def csr_mv(crow: torch.Tensor, col: torch.Tensor, val: torch.Tensor, v: torch.Te
     val = val.to(torch.float64).contiguous()
     v = v.to(torch.float64).contiguous()
     mean_nnz = float(col.numel()) / n
-    rc = L.alink_csr_mv_f64(crow.data_ptr(), col.data_ptr(), int(col.dtype == torch.int64), val.data_ptr(), n,
-                            v.data_ptr(), out.data_ptr(), mean_nnz, _lib.stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"alink_csr_mv_f64 failed: {rc}")
+    _lib.call("alink_csr_mv_f64", crow.data_ptr(), col.data_ptr(), int(col.dtype == torch.int64), val.data_ptr(), n,
+              v.data_ptr(), out.data_ptr(), mean_nnz, _lib.stream_ptr(dev))
     CSR_MV_CALLS += 1
     return out

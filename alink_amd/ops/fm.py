@@ -18,7 +18,7 @@ EPS = 1.0e-8
 
 
 def kernel_supported(fm, k: int) -> bool:
-    return fm.is_sparse and fm.val.is_cuda and 1 <= k <= 64 and (_lib.available() or not _lib.torch_fallback_allowed())
+    return fm.is_sparse and fm.val.is_cuda and 1 <= k <= 64 and _lib.kernels_enabled()
 
 
 def _csr(fm):
@@ -27,24 +27,21 @@ def _csr(fm):
 
 
 def fm_forward(fm, w, V, bias: float, want_vx: bool = True):
-    L = _lib.require()
     crow, col, val = _csr(fm)
     n = fm.nrows
     k = V.shape[1]
     dev = val.device
     y = torch.empty(n, dtype=torch.float64, device=dev)
     vx = torch.empty((n, k), dtype=torch.float64, device=dev) if want_vx else None
-    rc = L.alink_fm_forward_f64(crow.data_ptr(), col.data_ptr(), val.data_ptr(), n, k,
-                                None if w is None else w.data_ptr(), V.data_ptr(), float(bias), y.data_ptr(),
-                                None if vx is None else vx.data_ptr(), _lib.stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"alink_fm_forward_f64 failed: {rc}")
+    _lib.call("alink_fm_forward_f64", crow.data_ptr(), col.data_ptr(), val.data_ptr(), n, k,
+              None if w is None else w.data_ptr(), V.data_ptr(), float(bias), y.data_ptr(),
+              None if vx is None else vx.data_ptr(), _lib.stream_ptr(dev))
     return y, vx
 
 
 def fm_coord_update(fm, g, vx, sw_rows, w, sg_w, V, sg_V, use, lr: float, lam1: float, lam2: float):
     """In place on ``w, sg_w, V, sg_V, use`` (fp64, contiguous; ``w``/``sg_w`` may be None)."""
-    L = _lib.require()
+    _lib.require()
     crow, col, val = _csr(fm)
     if val.numel() == 0:
         return
@@ -57,11 +54,8 @@ def fm_coord_update(fm, g, vx, sw_rows, w, sg_w, V, sg_V, use, lr: float, lam1: 
     ent_row = rows[perm].contiguous()
     ent_val = val[perm].contiguous()
     k = V.shape[1]
-    rc = L.alink_fm_coord_update_f64(seg.data_ptr(), counts.numel(), coord.contiguous().data_ptr(),
-                                     ent_row.data_ptr(), ent_val.data_ptr(), g.contiguous().data_ptr(),
-                                     vx.contiguous().data_ptr(), sw_rows.to(torch.float64).contiguous().data_ptr(), k,
-                                     None if w is None else w.data_ptr(), None if sg_w is None else sg_w.data_ptr(),
-                                     V.data_ptr(), sg_V.data_ptr(), use.data_ptr(), float(lr), float(lam1),
-                                     float(lam2), EPS, _lib.stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"alink_fm_coord_update_f64 failed: {rc}")
+    _lib.call("alink_fm_coord_update_f64", seg.data_ptr(), counts.numel(), coord.contiguous().data_ptr(),
+              ent_row.data_ptr(), ent_val.data_ptr(), g.contiguous().data_ptr(), vx.contiguous().data_ptr(),
+              sw_rows.to(torch.float64).contiguous().data_ptr(), k, None if w is None else w.data_ptr(),
+              None if sg_w is None else sg_w.data_ptr(), V.data_ptr(), sg_V.data_ptr(), use.data_ptr(), float(lr),
+              float(lam1), float(lam2), EPS, _lib.stream_ptr(dev))

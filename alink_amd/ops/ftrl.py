@@ -21,7 +21,7 @@ __all__ = ["ftrl_hogwild", "ftrl_prox_hip", "ftrl_partial_margin_hip", "ftrl_sha
 
 def ftrl_hogwild(indptr: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, label: torch.Tensor, w: torch.Tensor,
                  n: torch.Tensor, z: torch.Tensor, alpha: float, beta: float, l1: float, l2: float) -> None:
-    L = _lib.require()
+    _lib.require()
     dev = w.device
     if not (w.is_cuda and w.dtype == torch.float64 and n.shape == w.shape and z.shape == w.shape):
         raise ValueError("ftrl_hogwild needs fp64 CUDA state vectors of one shape")
@@ -39,17 +39,12 @@ def ftrl_hogwild(indptr: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, lab
         raise ValueError("CSR arrays do not match the row pointer")
     st = _lib.stream_ptr(dev)
     bad = torch.zeros(1, dtype=torch.int32, device=dev)
-    rc = L.alink_ftrl_check_indices(idx.data_ptr(), nnz, w.shape[0], bad.data_ptr(), 1024, st)
-    if rc != 0:
-        raise RuntimeError(f"alink_ftrl_check_indices failed: {rc}")
+    _lib.call("alink_ftrl_check_indices", idx.data_ptr(), nnz, w.shape[0], bad.data_ptr(), 1024, st)
     if int(bad.item()) != 0:
         raise ValueError("feature index out of range of the model")
     grid = max(1, min((nrows + 3) // 4, 2048))
-    rc = L.alink_ftrl_hogwild_f64(indptr.data_ptr(), idx.data_ptr(), val.data_ptr(), label.data_ptr(), nrows,
-                                  w.data_ptr(), n.data_ptr(), z.data_ptr(), float(alpha), float(beta), float(l1),
-                                  float(l2), grid, st)
-    if rc != 0:
-        raise RuntimeError(f"alink_ftrl_hogwild_f64 failed: {rc}")
+    _lib.call("alink_ftrl_hogwild_f64", indptr.data_ptr(), idx.data_ptr(), val.data_ptr(), label.data_ptr(), nrows,
+              w.data_ptr(), n.data_ptr(), z.data_ptr(), float(alpha), float(beta), float(l1), float(l2), grid, st)
     # the racing w stores are last-writer-wins: re-derive w = prox(z, n) of every touched coordinate from the
     # exact atomic n/z sums (same stream, after the update kernel)
     ftrl_prox_hip(w, n, z, alpha, beta, l1, l2, coords=torch.unique(idx))
@@ -69,30 +64,24 @@ def _grid(n: int, per: int, cap: int = 4096) -> int:
 def ftrl_prox_hip(w: torch.Tensor, n: torch.Tensor, z: torch.Tensor, alpha: float, beta: float, l1: float, l2: float,
                   coords: torch.Tensor = None) -> None:
     """``w_i = prox(z_i, n_i)`` on the device for ``coords`` (int32) or every coordinate."""
-    L = _lib.require()
     m = w.shape[0] if coords is None else coords.shape[0]
     if coords is not None:
         coords = coords.to(device=w.device, dtype=torch.int32).contiguous()
-    rc = L.alink_ftrl_prox_f64(None if coords is None else coords.data_ptr(), m, w.data_ptr(), n.data_ptr(),
-                               z.data_ptr(), float(alpha), float(beta), float(l1), float(l2), _grid(m, 256),
-                               _lib.stream_ptr(w.device))
-    if rc != 0:
-        raise RuntimeError(f"alink_ftrl_prox_f64 failed: {rc}")
+    _lib.call("alink_ftrl_prox_f64", None if coords is None else coords.data_ptr(), m, w.data_ptr(), n.data_ptr(),
+              z.data_ptr(), float(alpha), float(beta), float(l1), float(l2), _grid(m, 256), _lib.stream_ptr(w.device))
 
 
 def ftrl_partial_margin_hip(indptr: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, w: torch.Tensor, lo: int,
                             hi: int) -> torch.Tensor:
     """Per-row ``sum_{lo <= i < hi} x_i w_i`` (``w`` = the owned shard) — one wave per row."""
-    L = _lib.require()
+    _lib.require()
     dev = w.device
     nrows = indptr.shape[0] - 1
     out = torch.zeros(max(nrows, 0), dtype=torch.float64, device=dev)
     if nrows <= 0:
         return out
-    rc = L.alink_ftrl_partial_margin_f64(indptr.data_ptr(), idx.data_ptr(), val.data_ptr(), nrows, w.data_ptr(),
-                                         int(lo), int(hi), out.data_ptr(), _grid(nrows, 4), _lib.stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"alink_ftrl_partial_margin_f64 failed: {rc}")
+    _lib.call("alink_ftrl_partial_margin_f64", indptr.data_ptr(), idx.data_ptr(), val.data_ptr(), nrows, w.data_ptr(),
+              int(lo), int(hi), out.data_ptr(), _grid(nrows, 4), _lib.stream_ptr(dev))
     return out
 
 
@@ -105,7 +94,7 @@ def ftrl_shard_update_hip(indptr: torch.Tensor, idx: torch.Tensor, val: torch.Te
     ``LONG_SEGMENT`` (``ftrl_coord_long_kernel``), one 512-thread speculative scan per segment longer than
     ``SCAN_SEGMENT`` (``ftrl_coord_scan_kernel``).  Segment boundaries, the long-segment lists and their lengths
     stay on the device (the kernels read the counts there): no host synchronisation in the whole update."""
-    L = _lib.require()
+    _lib.require()
     dev = w.device
     nrows = indptr.shape[0] - 1
     nnz = idx.numel()
@@ -130,23 +119,20 @@ def ftrl_shard_update_hip(indptr: torch.Tensor, idx: torch.Tensor, val: torch.Te
     coord = keys[first].contiguous()
     cnt = seg[1:nnz + 1] - seg[:nnz]
     live = (ar < nseg) & (coord < hi)
-    rc = L.alink_ftrl_coord_update_f64(seg.data_ptr(), nnz, nseg.data_ptr(), coord.data_ptr(), g.data_ptr(),
-                                       w.data_ptr(), n.data_ptr(), z.data_ptr(), int(lo), int(hi), float(alpha),
-                                       float(beta), float(l1), float(l2), LONG_SEGMENT, _grid(nnz, 256), st)
-    if rc != 0:
-        raise RuntimeError(f"alink_ftrl_coord_update_f64 failed: {rc}")
+    _lib.call("alink_ftrl_coord_update_f64", seg.data_ptr(), nnz, nseg.data_ptr(), coord.data_ptr(), g.data_ptr(),
+              w.data_ptr(), n.data_ptr(), z.data_ptr(), int(lo), int(hi), float(alpha), float(beta), float(l1),
+              float(l2), LONG_SEGMENT, _grid(nnz, 256), st)
     # segments longer than LONG_SEGMENT (the intercept, hot categorical values): compacted id lists + counts on
     # the device; the kernels stride over them from a fixed grid
-    for fn, sel, grid in ((L.alink_ftrl_coord_long_f64, live & (cnt > LONG_SEGMENT) & (cnt <= SCAN_SEGMENT), 256),
-                          (L.alink_ftrl_coord_scan_f64, live & (cnt > SCAN_SEGMENT), 16)):
+    for fn, sel, grid in (("alink_ftrl_coord_long_f64", live & (cnt > LONG_SEGMENT) & (cnt <= SCAN_SEGMENT), 256),
+                          ("alink_ftrl_coord_scan_f64", live & (cnt > SCAN_SEGMENT), 16)):
         pos = torch.cumsum(sel, 0) - 1
         lst = torch.empty(nnz + 1, dtype=torch.int64, device=dev)
         lst.index_put_((torch.where(sel, pos, nnz),), ar)
         num = pos[-1:] + 1
-        rc = fn(seg.data_ptr(), coord.data_ptr(), lst.data_ptr(), nnz, num.data_ptr(), g.data_ptr(), w.data_ptr(),
-                n.data_ptr(), z.data_ptr(), int(lo), float(alpha), float(beta), float(l1), float(l2), grid, st)
-        if rc != 0:
-            raise RuntimeError(f"{fn.__name__} failed: {rc}")
+        _lib.call(fn, seg.data_ptr(), coord.data_ptr(), lst.data_ptr(), nnz, num.data_ptr(), g.data_ptr(),
+                  w.data_ptr(), n.data_ptr(), z.data_ptr(), int(lo), float(alpha), float(beta), float(l1), float(l2),
+                  grid, st)
 
 
 def ftrl_dp_gradients(indptr: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, label: torch.Tensor,

@@ -34,10 +34,8 @@ def estep_torch(X0, mu0, W, logdet, rank, logw) -> Tuple[torch.Tensor, torch.Ten
 
 def estep(X0, mu0, W, logdet, rank, logw) -> Tuple[torch.Tensor, torch.Tensor]:
     k, d = mu0.shape
-    if not (X0.is_cuda and X0.dtype == torch.float64 and k <= KMAX) or \
-            (not _lib.available() and _lib.torch_fallback_allowed()):
+    if not (X0.is_cuda and X0.dtype == torch.float64 and k <= KMAX and _lib.kernels_enabled()):
         return estep_torch(X0, mu0, W, logdet, rank, logw)
-    L = _lib.require()
     n = X0.shape[0]
     dev = X0.device
     Wcat = W.permute(1, 0, 2).reshape(d, k * d).contiguous()          # [d, k*d]: column block j is W_j
@@ -49,10 +47,8 @@ def estep(X0, mu0, W, logdet, rank, logw) -> Tuple[torch.Tensor, torch.Tensor]:
     for s in range(0, n, rows):
         e = min(n, s + rows)
         Z = X0[s:e] @ Wcat
-        part = torch.empty(L.alink_gmm_grid(e - s), dtype=torch.float64, device=dev)
-        rc = L.alink_gmm_estep_f64(Z.data_ptr(), e - s, k, d, C.data_ptr(), cst.data_ptr(), R[s:e].data_ptr(),
-                                   part.data_ptr(), _lib.stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError(f"alink_gmm_estep_f64 failed: {rc}")
+        part = torch.empty(_lib.query("alink_gmm_grid", e - s), dtype=torch.float64, device=dev)
+        _lib.call("alink_gmm_estep_f64", Z.data_ptr(), e - s, k, d, C.data_ptr(), cst.data_ptr(), R[s:e].data_ptr(),
+                  part.data_ptr(), _lib.stream_ptr(dev))
         total = total + part.sum()
     return R, total

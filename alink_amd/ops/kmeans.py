@@ -220,7 +220,7 @@ def _assign_accumulate_hip(X: torch.Tensor, C: torch.Tensor, grid: Optional[int]
     ``skip`` (v10, static split): a device word written by ``update_centroids_hip(..., skip_tol=)``; when it is
     nonzero at run time the launch returns at once and the result is garbage (the caller drops it)."""
     global HIP_CALLS
-    L = _lib.require()
+    _lib.require()
     HIP_CALLS += 1
     dev = X.device
     k = C.shape[0]
@@ -234,7 +234,7 @@ def _assign_accumulate_hip(X: torch.Tensor, C: torch.Tensor, grid: Optional[int]
     ver = kernel_version(k)
     gkey = (ver, n, grid, dev.index)
     if gkey not in _GRID:      # per-shape launch geometry (one ctypes call per shape, not per superstep)
-        _GRID[gkey] = int(getattr(L, f"alink_kmeans_{ver}_grid")(n, grid if grid is not None else _num_cus(dev)))
+        _GRID[gkey] = _lib.query(f"alink_kmeans_{ver}_grid", n, grid if grid is not None else _num_cus(dev))
     grid = _GRID[gkey]
     key = (dev.index, grid)
     if key not in _BUF:
@@ -282,16 +282,15 @@ class _HostStat:
     kernel's last block writes directly, so a superstep needs neither a memset before the update nor a
     device->host copy after it.  If mapped host memory cannot be had, the update falls back to memset + copy."""
 
-    def __init__(self, L, dev):
+    def __init__(self, dev):
         import ctypes
         self.stat = torch.zeros(3, dtype=torch.int64, device=dev)
         self.host, self.dev_ptr, self._view = None, None, None
         h, d = ctypes.c_void_p(), ctypes.c_void_p()
         if os.environ.get("ALINK_KMEANS_HOST_STAT", "1") != "0" and \
-                L.alink_kmeans_host_stat_alloc(ctypes.byref(h), ctypes.byref(d)) == 0 and d.value:
+                _lib.query("alink_kmeans_host_stat_alloc", ctypes.byref(h), ctypes.byref(d)) == 0 and d.value:
             self._hptr, self.dev_ptr = h.value, d.value
             self._view = np.ctypeslib.as_array((ctypes.c_uint64 * 3).from_address(h.value))
-            self._L = L
         else:
             self.host = torch.empty(2, dtype=torch.int64, pin_memory=True)
         self.seq = 0
@@ -329,7 +328,7 @@ class _HostStat:
         try:
             if self._view is not None:
                 self._view = None
-                self._L.alink_kmeans_host_stat_free(self._hptr)
+                _lib.query("alink_kmeans_host_stat_free", self._hptr)
         except Exception:
             pass
 
@@ -354,12 +353,12 @@ def update_centroids_hip(buf: torch.Tensor, prev: Optional[torch.Tensor], deferr
     writes a device word = (some cluster empty, or prev given and max shift < skip_tol) — ``read.skip`` is that word (None
     when unavailable), for a speculative ``assign_accumulate_hip(..., skip=read.skip)`` to return at once on
     convergence; the caller must drop such a result whenever ``shift < skip_tol`` or a cluster is empty."""
-    L = _lib.require()
+    _lib.require()
     dev = buf.device
     k = buf.shape[0]
     cpad, ninit = _prep_operands(dev)
     if dev.index not in _STAT:
-        _STAT[dev.index] = _HostStat(L, dev)
+        _STAT[dev.index] = _HostStat(dev)
     hs = _STAT[dev.index]
     stat = hs.stat
     use_prev = prev is not None and prev.is_cuda and prev.dtype == torch.float64 and tuple(prev.shape) == (k, HIP_D)
@@ -633,22 +632,21 @@ def serpentine_reverse(step: int) -> bool:
 
 def assign_accumulate(X: torch.Tensor, C: torch.Tensor, weights: Optional[torch.Tensor] = None,
                       reverse: bool = False) -> torch.Tensor:
-    hip_ok = _lib.available() or not _lib.torch_fallback_allowed()
-    if weights is None and hip_supported(X, C.shape[0]) and hip_ok:
+    if weights is None and hip_supported(X, C.shape[0]) and _lib.kernels_enabled():
         return assign_accumulate_hip(X, C, reverse=reverse)
     with _timed(X.device):
         if weights is None and _d64.dense64_selected(X, C.shape[0]) and X.shape[0] > 0:
             return _d64.assign_accumulate(X, C)     # raises without the library unless the fall-back is allowed
-        if general_supported(X, C.shape[0]) and hip_ok:
+        if general_supported(X, C.shape[0]) and _lib.kernels_enabled():
             return assign_accumulate_general_hip(X, C, weights)
-        if f32_supported(X, C.shape[0]) and hip_ok:
+        if f32_supported(X, C.shape[0]) and _lib.kernels_enabled():
             return assign_accumulate_f32_hip(X, C, weights)
         return assign_accumulate_torch(X, C, weights)
 
 
 def assign(X: torch.Tensor, C: torch.Tensor, chunk: int = 1 << 20) -> Tuple[torch.Tensor, torch.Tensor]:
     """Nearest centroid index and squared euclidean distance for every row."""
-    if nearest_supported(X) and (_lib.available() or not _lib.torch_fallback_allowed()):
+    if nearest_supported(X) and _lib.kernels_enabled():
         idx, d2 = nearest_hip(X, C)
         return idx.to(torch.int64), d2.to(torch.float64)
     low = X.dtype in (torch.bfloat16, torch.float16)

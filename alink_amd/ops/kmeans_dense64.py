@@ -57,12 +57,7 @@ def _use_hip(X: torch.Tensor, k: int) -> bool:
     if not dense64_supported(X, k):
         raise ValueError("dense fp64 KMeans on the GPU needs contiguous fp64 [n, d] rows with 1 <= d <= "
                          f"{DENSE_DMAX}, fewer than 2^31 rows and k >= 1")
-    if _lib.available():
-        return True
-    if _lib.torch_fallback_allowed():
-        return False
-    _lib.require()      # raises: no quiet fall-back on a GPU
-    return False
+    return _lib.kernels_enabled()
 
 
 def _dist_code(dist_type: str) -> int:

@@ -345,11 +345,8 @@ def rows(X, dist_type: str) -> Rows:
         if dt not in ("EUCLIDEAN", "COSINE"):
             raise ValueError(f"sparse KMeans supports EUCLIDEAN and COSINE, not {dist_type}")
         return _SparseRows(X, dt)
-    if dt == "EUCLIDEAN" and kops.nearest_supported(X):
-        if _lib.available():
-            return _Bf16Rows(X, dt)
-        if not _lib.torch_fallback_allowed():
-            _lib.require()      # raises: no quiet fall-back on a GPU
+    if dt == "EUCLIDEAN" and kops.nearest_supported(X) and _lib.kernels_enabled():
+        return _Bf16Rows(X, dt)
     # an empty partition launches nothing and stays on the torch kind
     if dt in ("EUCLIDEAN", "COSINE") and X.shape[0] > 0 and kd64.dense64_selected(X, 1):
         return _Dense64Rows(X, dt)

@@ -63,12 +63,7 @@ def _use_hip(fm) -> bool:
         return False
     if not sparse_supported(fm):
         raise ValueError("sparse KMeans on the GPU needs fp64 values, int32/int64 columns and fewer than 2^31 rows")
-    if _lib.available():
-        return True
-    if _lib.torch_fallback_allowed():
-        return False
-    _lib.require()      # raises: no quiet fall-back on a GPU
-    return False
+    return _lib.kernels_enabled()
 
 
 def _dist_code(dist_type: str) -> int:

@@ -18,12 +18,12 @@ GIBBS_VARIANT = int(__import__("os").environ.get("ALINK_LDA_GIBBS_VARIANT", "1")
 
 
 def kernel_supported(dev) -> bool:
-    return torch.device(dev).type == "cuda" and (_lib.available() or not _lib.torch_fallback_allowed())
+    return torch.device(dev).type == "cuda" and _lib.kernels_enabled()
 
 
 def gibbs_sweep(d_tok, w_tok, z, nd, nw, nk, alpha: float, beta: float, V: int, u,
                 variant: int = None) -> torch.Tensor:
-    L = _lib.require()
+    _lib.require()
     T = z.numel()
     out = torch.empty_like(z)
     if T == 0:
@@ -32,19 +32,17 @@ def gibbs_sweep(d_tok, w_tok, z, nd, nw, nk, alpha: float, beta: float, V: int, 
     nd = nd.to(torch.int32).contiguous()
     nw = nw.to(torch.int32).contiguous()
     nk = nk.to(torch.float64).contiguous()
-    rc = L.alink_lda_gibbs(d_tok.contiguous().data_ptr(), w_tok.contiguous().data_ptr(), z.contiguous().data_ptr(), T,
-                           K, nd.data_ptr(), nw.data_ptr(), nk.data_ptr(), float(alpha), float(beta),
-                           float(V * beta), u.to(torch.float64).contiguous().data_ptr(), out.data_ptr(),
-                           GIBBS_VARIANT if variant is None else int(variant), _lib.stream_ptr(z.device))
-    if rc != 0:
-        raise RuntimeError(f"alink_lda_gibbs failed: {rc}")
+    _lib.call("alink_lda_gibbs", d_tok.contiguous().data_ptr(), w_tok.contiguous().data_ptr(),
+              z.contiguous().data_ptr(), T, K, nd.data_ptr(), nw.data_ptr(), nk.data_ptr(), float(alpha), float(beta),
+              float(V * beta), u.to(torch.float64).contiguous().data_ptr(), out.data_ptr(),
+              GIBBS_VARIANT if variant is None else int(variant), _lib.stream_ptr(z.device))
     return out
 
 
 def estep(doc, word, cts, n_docs: int, expElogbeta_T, alpha, gamma0, max_iter: int = 100, tol: float = 1e-3):
     """Online-VB E-step on the GPU: (gamma [D, K], expElogtheta [D, K], phinorm [T]) for tokens grouped by
     document (``doc`` non-decreasing).  ``expElogbeta_T`` [V, K]; K <= 256."""
-    L = _lib.require()
+    _lib.require()
     dev = gamma0.device
     D, K = gamma0.shape
     T = doc.numel()
@@ -63,11 +61,9 @@ def estep(doc, word, cts, n_docs: int, expElogbeta_T, alpha, gamma0, max_iter: i
     gamma = torch.empty((D, K), dtype=torch.float64, device=dev)
     et = torch.empty((D, K), dtype=torch.float64, device=dev)
     phin = torch.empty(max(T, 1), dtype=torch.float64, device=dev)
-    rc = L.alink_lda_estep(off.data_ptr(), word.data_ptr(), cts.data_ptr(), D, K, eb.data_ptr(), al.data_ptr(),
-                           g0.data_ptr(), int(max_iter), float(tol), gamma.data_ptr(), et.data_ptr(), phin.data_ptr(),
-                           _lib.stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"alink_lda_estep failed: {rc}")
+    _lib.call("alink_lda_estep", off.data_ptr(), word.data_ptr(), cts.data_ptr(), D, K, eb.data_ptr(), al.data_ptr(),
+              g0.data_ptr(), int(max_iter), float(tol), gamma.data_ptr(), et.data_ptr(), phin.data_ptr(),
+              _lib.stream_ptr(dev))
     phin = phin[:T]
     if order is not None:
         inv = torch.empty_like(order)

@@ -51,7 +51,7 @@ def hip_linear_supported(X: torch.Tensor) -> bool:
 
 def linear_grad_hip(X: torch.Tensor, y: torch.Tensor, w: torch.Tensor, coef: torch.Tensor, code: int,
                     prm: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    L = _lib.require()
+    _lib.require()
     if not hip_linear_supported(X):
         raise ValueError(f"linear_grad_hip needs a contiguous fp64 [n, d<={MAX_D}] CUDA tensor")
     n, d = X.shape
@@ -61,7 +61,7 @@ def linear_grad_hip(X: torch.Tensor, y: torch.Tensor, w: torch.Tensor, coef: tor
     c = coef[:d].to(device=dev, dtype=torch.float64).contiguous()
     if y.shape[0] != n or w.shape[0] != n:
         raise ValueError("label / weight length mismatch")
-    pad = int(L.alink_linear_grad_pad(d))
+    pad = _lib.query("alink_linear_grad_pad", d)
     wide = d > 32
     # narrow: one row per lane (256 rows per block); wide: one row group per wave, 2 blocks per CU resident
     nblk = max(1, min((n + 255) // 256, 2048)) if not wide else max(1, min((n + 7) // 8, 1024))
@@ -69,11 +69,9 @@ def linear_grad_hip(X: torch.Tensor, y: torch.Tensor, w: torch.Tensor, coef: tor
     if key not in _SLABS:
         _SLABS[key] = torch.empty(nblk * (pad + 2), dtype=torch.float64, device=dev)
     out = torch.empty(d + 2, dtype=torch.float64, device=dev)
-    fn = L.alink_linear_grad_wide_f64 if wide else L.alink_linear_grad_f64
-    rc = fn(X.data_ptr(), y.data_ptr(), w.data_ptr(), c.data_ptr(), n, d, int(code), float(prm),
-            _SLABS[key].data_ptr(), nblk, out.data_ptr(), _lib.stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"alink_linear_grad{'_wide' if wide else ''}_f64 failed: {rc}")
+    _lib.call("alink_linear_grad_wide_f64" if wide else "alink_linear_grad_f64", X.data_ptr(), y.data_ptr(),
+              w.data_ptr(), c.data_ptr(), n, d, int(code), float(prm), _SLABS[key].data_ptr(), nblk, out.data_ptr(),
+              _lib.stream_ptr(dev))
     g = out[:d]
     if coef.shape[0] > d:
         g = torch.cat([g, torch.zeros(coef.shape[0] - d, dtype=g.dtype, device=dev)])
@@ -93,7 +91,7 @@ def search_losses_hip(X: torch.Tensor, y: torch.Tensor, w: torch.Tensor, coef: t
                       code: int, prm: float, beta: float, nsteps: int) -> torch.Tensor:
     """K14: ``[sum_i w_i l(x_i.coef - s beta x_i.dir, y_i) for s < nsteps]`` in one pass over the dense fp64 X
     (``csrc/linear.hip`` linear_search_kernel; the torch form is an [n,d]x[d,2] fp64 GEMM plus elementwise)."""
-    L = _lib.require()
+    _lib.require()
     if not hip_linear_supported(X) or not 1 <= nsteps <= SEARCH_MAX_STEPS:
         raise ValueError("search_losses_hip needs a contiguous fp64 [n, d<=1024] CUDA tensor and <= 16 steps")
     n, d = X.shape
@@ -107,17 +105,14 @@ def search_losses_hip(X: torch.Tensor, y: torch.Tensor, w: torch.Tensor, coef: t
     if key not in _SLABS:
         _SLABS[key] = torch.empty(nblk * (SEARCH_MAX_STEPS + 2), dtype=torch.float64, device=dev)
     out = torch.empty(SEARCH_MAX_STEPS, dtype=torch.float64, device=dev)
-    rc = L.alink_linear_search_f64(X.data_ptr(), y.data_ptr(), w.data_ptr(), c.data_ptr(), dv.data_ptr(), n, d,
-                                   int(code), float(prm), float(beta), int(nsteps), _SLABS[key].data_ptr(), nblk,
-                                   out.data_ptr(), _lib.stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"alink_linear_search_f64 failed: {rc}")
+    _lib.call("alink_linear_search_f64", X.data_ptr(), y.data_ptr(), w.data_ptr(), c.data_ptr(), dv.data_ptr(), n, d,
+              int(code), float(prm), float(beta), int(nsteps), _SLABS[key].data_ptr(), nblk, out.data_ptr(),
+              _lib.stream_ptr(dev))
     return out[:nsteps]
 
 
 def hip_sparse_supported(fm) -> bool:
-    return fm is not None and getattr(fm, "is_sparse", False) and fm.val.is_cuda and \
-        (_lib.available() or not _lib.torch_fallback_allowed())
+    return fm is not None and getattr(fm, "is_sparse", False) and fm.val.is_cuda and _lib.kernels_enabled()
 
 
 def _csc(fm):
@@ -142,7 +137,7 @@ def _csc(fm):
 def sparse_grad_hip(fm, y: torch.Tensor, w: torch.Tensor, coef: torch.Tensor, code: int, prm: float = 0.0):
     """(sum_i w_i l'(x_i.coef, y_i) x_i [d], sum_i w_i l(.), sum_i w_i) over a CSR FeatureMatrix on the GPU:
     row pass (wave per row) + column gather over the cached CSC copy (wave per column), no atomics."""
-    L = _lib.require()
+    _lib.require()
     dev = fm.val.device
     n = fm.nrows
     cptr, rows_of, cval, col32, val64 = _csc(fm)
@@ -155,16 +150,12 @@ def sparse_grad_hip(fm, y: torch.Tensor, w: torch.Tensor, coef: torch.Tensor, co
     lw = torch.empty(n, dtype=torch.float64, device=dev)
     st = _lib.stream_ptr(dev)
     crow = fm.crow.to(torch.int64).contiguous()
-    rc = L.alink_csr_row_deriv_f64(crow.data_ptr(), col32.data_ptr(), val64.data_ptr(), y.data_ptr(), w.data_ptr(),
-                                   c.data_ptr(), n, int(code), float(prm), g.data_ptr(), lw.data_ptr(), st)
-    if rc != 0:
-        raise RuntimeError(f"alink_csr_row_deriv_f64 failed: {rc}")
+    _lib.call("alink_csr_row_deriv_f64", crow.data_ptr(), col32.data_ptr(), val64.data_ptr(), y.data_ptr(),
+              w.data_ptr(), c.data_ptr(), n, int(code), float(prm), g.data_ptr(), lw.data_ptr(), st)
     grad = torch.zeros(coef.shape[0], dtype=torch.float64, device=dev)
     out = torch.empty(d, dtype=torch.float64, device=dev)
-    rc = L.alink_csc_gather_f64(cptr.data_ptr(), rows_of.data_ptr(), cval.data_ptr(), g.data_ptr(), d,
-                                out.data_ptr(), st)
-    if rc != 0:
-        raise RuntimeError(f"alink_csc_gather_f64 failed: {rc}")
+    _lib.call("alink_csc_gather_f64", cptr.data_ptr(), rows_of.data_ptr(), cval.data_ptr(), g.data_ptr(), d,
+              out.data_ptr(), st)
     m = min(d, coef.shape[0])
     grad[:m] = out[:m]
     return grad, lw.sum(), w.sum()

@@ -22,8 +22,7 @@ KMAX = 32
 
 
 def kernel_supported(X: torch.Tensor, layers: Sequence[int]) -> bool:
-    return X.is_cuda and X.dtype == torch.float64 and 0 < int(layers[-1]) <= KMAX and \
-        (_lib.available() or not _lib.torch_fallback_allowed())
+    return X.is_cuda and X.dtype == torch.float64 and 0 < int(layers[-1]) <= KMAX and _lib.kernels_enabled()
 
 
 def _unpack(w: torch.Tensor, layers):
@@ -38,7 +37,7 @@ def _unpack(w: torch.Tensor, layers):
 def mlp_grad(X: torch.Tensor, y: torch.Tensor, w: torch.Tensor, coef: torch.Tensor, layers) \
         -> Tuple[torch.Tensor, torch.Tensor]:
     """(flat gradient of sum_i w_i CE_i in the coef layout, weighted loss sum)."""
-    L = _lib.require()
+    _lib.require()
     dev = X.device
     st = _lib.stream_ptr(dev)
     params = _unpack(coef, layers)
@@ -50,26 +49,20 @@ def mlp_grad(X: torch.Tensor, y: torch.Tensor, w: torch.Tensor, coef: torch.Tens
     h = X
     for W, b in params[:-1]:
         z = h @ W
-        rc = L.alink_bias_sigmoid_f64(z.data_ptr(), n, z.shape[1], b.contiguous().data_ptr(), st)
-        if rc != 0:
-            raise RuntimeError(f"alink_bias_sigmoid_f64 failed: {rc}")
+        _lib.call("alink_bias_sigmoid_f64", z.data_ptr(), n, z.shape[1], b.contiguous().data_ptr(), st)
         hs.append(z)
         h = z
     Wo, bo = params[-1]
     zo = torch.addmm(bo, h, Wo).contiguous()
     D = torch.empty_like(zo)
-    part = torch.zeros(max(1, L.alink_softmax_grid(n)), dtype=torch.float64, device=dev)
-    rc = L.alink_softmax_full_grad_f64(zo.data_ptr(), y.data_ptr(), w.data_ptr(), n, zo.shape[1], D.data_ptr(),
-                                       part.data_ptr(), st)
-    if rc != 0:
-        raise RuntimeError(f"alink_softmax_full_grad_f64 failed: {rc}")
+    part = torch.zeros(max(1, _lib.query("alink_softmax_grid", n)), dtype=torch.float64, device=dev)
+    _lib.call("alink_softmax_full_grad_f64", zo.data_ptr(), y.data_ptr(), w.data_ptr(), n, zo.shape[1], D.data_ptr(),
+              part.data_ptr(), st)
     grads = [None] * len(params)
     for i in range(len(params) - 1, -1, -1):
         W, _ = params[i]
         grads[i] = (tn_matmul(hs[i], D).reshape(-1), D.sum(0))
         if i > 0:
             D = (D @ W.T).contiguous()
-            rc = L.alink_sigmoid_bwd_f64(D.data_ptr(), hs[i].data_ptr(), D.numel(), st)
-            if rc != 0:
-                raise RuntimeError(f"alink_sigmoid_bwd_f64 failed: {rc}")
+            _lib.call("alink_sigmoid_bwd_f64", D.data_ptr(), hs[i].data_ptr(), D.numel(), st)
     return torch.cat([t for gw, gb in grads for t in (gw, gb)]), part.sum()

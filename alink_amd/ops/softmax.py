@@ -50,41 +50,35 @@ def softmax_search_torch(ec, ed, y, w, beta: float, nsteps: int) -> torch.Tensor
 
 def _kernel_ok(eta: torch.Tensor) -> bool:
     return eta.is_cuda and eta.dtype == torch.float64 and eta.dim() == 2 and 0 < eta.shape[1] <= KMAX and \
-        (_lib.available() or not _lib.torch_fallback_allowed())
+        _lib.kernels_enabled()
 
 
 def softmax_grad(eta, y, w) -> Tuple[torch.Tensor, torch.Tensor]:
     if not _kernel_ok(eta):
         return softmax_grad_torch(eta, y, w)
-    L = _lib.require()
     n, k1 = eta.shape
     eta = eta.contiguous()
     y = y.to(torch.float64).contiguous()
     w = w.to(torch.float64).contiguous()
     assert y.numel() == n and w.numel() == n
     R = torch.empty_like(eta)
-    part = torch.zeros(max(1, L.alink_softmax_grid(n)), dtype=torch.float64, device=eta.device)
-    rc = L.alink_softmax_grad_f64(eta.data_ptr(), y.data_ptr(), w.data_ptr(), n, k1, R.data_ptr(), part.data_ptr(),
-                                  _lib.stream_ptr(eta.device))
-    if rc != 0:
-        raise RuntimeError(f"alink_softmax_grad_f64 failed: {rc}")
+    part = torch.zeros(max(1, _lib.query("alink_softmax_grid", n)), dtype=torch.float64, device=eta.device)
+    _lib.call("alink_softmax_grad_f64", eta.data_ptr(), y.data_ptr(), w.data_ptr(), n, k1, R.data_ptr(),
+              part.data_ptr(), _lib.stream_ptr(eta.device))
     return R, part.sum()
 
 
 def softmax_search(ec, ed, y, w, beta: float, nsteps: int) -> torch.Tensor:
     if not _kernel_ok(ec) or nsteps > 64:
         return softmax_search_torch(ec, ed, y, w, beta, nsteps)
-    L = _lib.require()
     n, k1 = ec.shape
     assert ed.shape == ec.shape
     ec, ed = ec.contiguous(), ed.to(torch.float64).contiguous()
     y = y.to(torch.float64).contiguous()
     w = w.to(torch.float64).contiguous()
-    part = torch.zeros((max(1, L.alink_softmax_grid(n)), nsteps), dtype=torch.float64, device=ec.device)
-    rc = L.alink_softmax_search_f64(ec.data_ptr(), ed.data_ptr(), y.data_ptr(), w.data_ptr(), n, k1, float(beta),
-                                    int(nsteps), part.data_ptr(), _lib.stream_ptr(ec.device))
-    if rc != 0:
-        raise RuntimeError(f"alink_softmax_search_f64 failed: {rc}")
+    part = torch.zeros((max(1, _lib.query("alink_softmax_grid", n)), nsteps), dtype=torch.float64, device=ec.device)
+    _lib.call("alink_softmax_search_f64", ec.data_ptr(), ed.data_ptr(), y.data_ptr(), w.data_ptr(), n, k1,
+              float(beta), int(nsteps), part.data_ptr(), _lib.stream_ptr(ec.device))
     return part.sum(0)
 
 

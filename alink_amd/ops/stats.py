@@ -17,7 +17,7 @@ TB = 256
 
 
 def kernel_supported(X: torch.Tensor) -> bool:
-    return X.is_cuda and X.dim() == 2 and X.dtype in _DT and (_lib.available() or not _lib.torch_fallback_allowed())
+    return X.is_cuda and X.dim() == 2 and X.dtype in _DT and _lib.kernels_enabled()
 
 
 def colstats_torch(X: torch.Tensor) -> dict:
@@ -37,16 +37,13 @@ def colstats(X: torch.Tensor, use_kernel: bool = None) -> dict:
         use_kernel = kernel_supported(X)
     if not use_kernel:
         return colstats_torch(X)
-    L = _lib.require()
     X = X.contiguous()
     n, d = X.shape
     chunks = (d + TB - 1) // TB
     phases = max(1, TB // min(d, TB))
     slabs = int(max(1, min((n + 4 * phases - 1) // (4 * phases), max(1, 2048 // chunks))))
     part = torch.empty((slabs, 6, d), dtype=torch.float64, device=X.device)
-    rc = L.alink_colstats(X.data_ptr(), n, d, _DT[X.dtype], slabs, part.data_ptr(), _lib.stream_ptr(X.device))
-    if rc != 0:
-        raise RuntimeError(f"alink_colstats failed: {rc}")
+    _lib.call("alink_colstats", X.data_ptr(), n, d, _DT[X.dtype], slabs, part.data_ptr(), _lib.stream_ptr(X.device))
     tot = part[:, [0, 1, 2, 5]].sum(0)
     return {"sum": tot[0], "sum2": tot[1], "l1": tot[2], "min": part[:, 3].amin(0), "max": part[:, 4].amax(0),
             "nnz": tot[3]}

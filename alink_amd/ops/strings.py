@@ -65,13 +65,10 @@ def hash_bytes(block: StringBlock, seed: int = 0) -> torch.Tensor:
     if n == 0:
         return torch.zeros(0, dtype=torch.int32, device=dev)
     if dev.type == "cuda":
-        L = _lib.require()
         data = block.data if block.nbytes else torch.zeros(1, dtype=torch.uint8, device=dev)
         out = torch.empty(n, dtype=torch.int32, device=dev)
-        rc = L.alink_murmur3_bytes(data.data_ptr(), block.offsets.contiguous().data_ptr(), n, seed & 0xFFFFFFFF,
-                                   out.data_ptr(), _lib.stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError(f"alink_murmur3_bytes failed: {rc}")
+        _lib.call("alink_murmur3_bytes", data.data_ptr(), block.offsets.contiguous().data_ptr(), n, seed & 0xFFFFFFFF,
+                  out.data_ptr(), _lib.stream_ptr(dev))
         return out
     from .. import _native
     data, off = block.data.numpy(), block.offsets.numpy()
@@ -119,7 +116,7 @@ def murmur3_multi_index(blocks, prefixes, nf: int, seed: int = 0):
         return None
     n = len(blocks[0])
     dev = blocks[0].device
-    L = _lib.require()
+    _lib.require()
     a = _MultiHashArgs()
     keep = []
     pos = 0
@@ -139,10 +136,8 @@ def murmur3_multi_index(blocks, prefixes, nf: int, seed: int = 0):
     a.pstart[m] = pos
     idx = torch.empty((m, n), dtype=torch.int32, device=dev)
     valid = torch.empty((m, n), dtype=torch.uint8, device=dev)
-    rc = L.alink_murmur3_multi_index(ctypes.addressof(a), m, n, seed & 0xFFFFFFFF, int(nf), idx.data_ptr(),
-                                     valid.data_ptr(), _lib.stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"alink_murmur3_multi_index failed: {rc}")
+    _lib.call("alink_murmur3_multi_index", ctypes.addressof(a), m, n, seed & 0xFFFFFFFF, int(nf), idx.data_ptr(),
+              valid.data_ptr(), _lib.stream_ptr(dev))
     return idx, valid
 
 
@@ -155,14 +150,12 @@ def murmur3_utf8_index(block: StringBlock, nf: int, prefix: str = "", seed: int 
     pu = np.frombuffer(prefix.encode("utf-16-le"), dtype=np.uint16).copy() if prefix else np.zeros(1, np.uint16)
     plen = len(prefix.encode("utf-16-le")) // 2
     if dev.type == "cuda":
-        L = _lib.require()
+        _lib.require()
         data = block.data if block.nbytes else torch.zeros(1, dtype=torch.uint8, device=dev)
         p = _device_prefix(pu, prefix, dev)
         out = torch.empty(n, dtype=torch.int32, device=dev)
-        rc = L.alink_murmur3_utf8_index(data.data_ptr(), block.offsets.contiguous().data_ptr(), n, p.data_ptr(),
-                                        plen, seed & 0xFFFFFFFF, int(nf), None, out.data_ptr(), _lib.stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError(f"alink_murmur3_utf8_index failed: {rc}")
+        _lib.call("alink_murmur3_utf8_index", data.data_ptr(), block.offsets.contiguous().data_ptr(), n, p.data_ptr(),
+                  plen, seed & 0xFFFFFFFF, int(nf), None, out.data_ptr(), _lib.stream_ptr(dev))
         return out.to(torch.int64)
     from .. import _native
     h = _native.murmur3_utf8(block.data.numpy(), block.offsets.numpy(), prefix, seed)

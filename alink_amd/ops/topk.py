@@ -28,8 +28,7 @@ def pad_rank(r: int) -> int:
 
 
 def kernel_supported(Q: torch.Tensor, K: int) -> bool:
-    return Q.is_cuda and pad_rank(Q.shape[1]) <= 64 and 1 <= K <= KMAX and \
-        (_lib.available() or not _lib.torch_fallback_allowed())
+    return Q.is_cuda and pad_rank(Q.shape[1]) <= 64 and 1 <= K <= KMAX and _lib.kernels_enabled()
 
 
 class TopKState:
@@ -57,7 +56,6 @@ def merge(state: TopKState, Q: torch.Tensor, T: torch.Tensor, item_base: int = 0
     if use_kernel is None:
         use_kernel = kernel_supported(Q, state.K)
     if use_kernel:
-        L = _lib.require()
         R = pad_rank(Q.shape[1])
         Qp, Tp = _pad(Q, R), _pad(T.to(Q.device), R)
         # split the items too when the query blocks alone cannot fill the chip (>= 2 workgroups per CU)
@@ -72,10 +70,8 @@ def merge(state: TopKState, Q: torch.Tensor, T: torch.Tensor, item_base: int = 0
             idx = torch.full((slices, m, state.K), -1, dtype=torch.int32, device=Q.device)
             val[0].copy_(state.val)
             idx[0].copy_(state.idx)
-        rc = L.alink_topk_cross_f32(Qp.data_ptr(), m, Tp.data_ptr(), n, int(item_base), R, state.K,
-                                    val.data_ptr(), idx.data_ptr(), slices, per, _lib.stream_ptr(Q.device))
-        if rc != 0:
-            raise RuntimeError(f"alink_topk_cross_f32 failed: {rc}")
+        _lib.call("alink_topk_cross_f32", Qp.data_ptr(), m, Tp.data_ptr(), n, int(item_base), R, state.K,
+                  val.data_ptr(), idx.data_ptr(), slices, per, _lib.stream_ptr(Q.device))
         if slices > 1:
             # plane order = item order, and a stable sort keeps the earlier plane on equal scores
             allv = val.permute(1, 0, 2).reshape(m, slices * state.K)

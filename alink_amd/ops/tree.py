@@ -28,7 +28,7 @@ __all__ = ["FmStats", "histogram", "histogram_groups", "histogram_torch", "route
 
 def gpu_kernels_ok() -> bool:
     """HIP kernels are used on GPU tensors unless the library is missing AND the torch fallback is allowed."""
-    return _lib.available() or not _lib.torch_fallback_allowed()
+    return _lib.kernels_enabled()
 
 
 def _num_cus(device) -> int:
@@ -101,11 +101,8 @@ def gather_rows(q: torch.Tensor, p: torch.Tensor, order: torch.Tensor = None):
     qo = torch.empty((n, 4), dtype=torch.int32, device=dev)
     oo = torch.empty(n, dtype=torch.int32, device=dev) if order is not None else None
     if n:
-        L = _lib.require()
-        rc = L.alink_tree_gather_rows(q.data_ptr(), None if order is None else order.data_ptr(), p.data_ptr(), n,
-                                      qo.data_ptr(), None if oo is None else oo.data_ptr(), _lib.stream_ptr(dev))
-        if rc != 0:
-            raise RuntimeError(f"alink_tree_gather_rows failed: {rc}")
+        _lib.call("alink_tree_gather_rows", q.data_ptr(), None if order is None else order.data_ptr(), p.data_ptr(), n,
+                  qo.data_ptr(), None if oo is None else oo.data_ptr(), _lib.stream_ptr(dev))
     return qo, oo
 
 
@@ -186,7 +183,7 @@ class FmStats:
         self.inv = torch.tensor([1.0 / x for x in scales], dtype=torch.float64, device=dev)
 
 
-def _histogram_fm(L, bins, slot, stats, nslots: int, B: int, prep: "FmStats" = None, fgroups=None,
+def _histogram_fm(bins, slot, stats, nslots: int, B: int, prep: "FmStats" = None, fgroups=None,
                   tro: "RowOrder" = None, slot_nodes=None) -> torch.Tensor:
     """``tree_hist_fm`` path: rows grouped by slot (stable sort of the slot keys, or the identity when every row
     is in slot 0), statistics quantised to int64 fixed point (``prep``, or here) and gathered into that order,
@@ -235,13 +232,10 @@ def _histogram_fm(L, bins, slot, stats, nslots: int, B: int, prep: "FmStats" = N
     cr = torch.from_numpy(chunk_rows).to(dev)
     scn = torch.from_numpy(slot_chunk).to(dev)
     slab = torch.empty(max(nchunks, 1) * nfg * B * (2 if prep.pack else S) * 32, dtype=torch.int64, device=dev)
-    rc = L.alink_tree_hist_fm(bins.data_ptr(), F, None if ridx is None else ridx.data_ptr(), q.data_ptr(),
-                              cr.data_ptr(), nchunks, scn.data_ptr(), nslots, S, B,
-                              None if fgl is None else fgl.data_ptr(), nfg, int(fgl is not None),
-                              prep.inv.data_ptr(), slab.data_ptr(), hist.data_ptr(), _lib.stream_ptr(dev),
-                              int(prep.pack))
-    if rc != 0:
-        raise RuntimeError(f"alink_tree_hist_fm failed: {rc}")
+    _lib.call("alink_tree_hist_fm", bins.data_ptr(), F, None if ridx is None else ridx.data_ptr(), q.data_ptr(),
+              cr.data_ptr(), nchunks, scn.data_ptr(), nslots, S, B, None if fgl is None else fgl.data_ptr(), nfg,
+              int(fgl is not None), prep.inv.data_ptr(), slab.data_ptr(), hist.data_ptr(), _lib.stream_ptr(dev),
+              int(prep.pack))
     return hist
 
 
@@ -259,8 +253,8 @@ def histogram_groups(bins: torch.Tensor, slot: torch.Tensor, stats: torch.Tensor
     if prep is None and S == 3 and FM_PACK and fm_eligible(bins, S, B, pack=True):
         prep = FmStats(stats)
     if fm_eligible(bins, S, B, pack=prep is not None and prep.pack):
-        return _histogram_fm(_lib.require(), bins, slot.to(torch.int32).contiguous(), stats, nslots, B, prep,
-                             fgroups=fgroups, tro=tro, slot_nodes=slot_nodes)
+        return _histogram_fm(bins, slot.to(torch.int32).contiguous(), stats, nslots, B, prep, fgroups=fgroups,
+                             tro=tro, slot_nodes=slot_nodes)
     feats = torch.tensor([g * 32 + l for g in fgroups for l in range(32)], dtype=torch.long)
     out = torch.zeros((feats.numel(), nslots, B, S), dtype=torch.float32 if bins.is_cuda else torch.float64,
                       device=bins.device)
@@ -286,9 +280,8 @@ def histogram(bins: torch.Tensor, slot: torch.Tensor, stats: torch.Tensor, nslot
     quantised for the fixed-point kernel (``FmStats(stats)``, reused across the levels of a tree)."""
     if not bins.is_cuda:
         return histogram_torch(bins, slot, stats, nslots, B)
-    if not _lib.available() and _lib.torch_fallback_allowed():
+    if not _lib.kernels_enabled():
         return histogram_torch(bins, slot, stats, nslots, B, dtype=torch.float32)
-    L = _lib.require()
     n, F = bins.shape
     S = stats.shape[1]
     if bins.dtype != torch.uint8 or not bins.is_contiguous():
@@ -302,15 +295,13 @@ def histogram(bins: torch.Tensor, slot: torch.Tensor, stats: torch.Tensor, nslot
     if prep is None and S == 3 and FM_PACK and fm_eligible(bins, S, B, variant, pack=True):
         prep = FmStats(stats)               # decides whether the packed (g, count) build applies
     if fm_eligible(bins, S, B, variant, pack=prep is not None and prep.pack) and nslots > 0:
-        return _histogram_fm(L, bins, slot, stats, nslots, B, prep, tro=tro, slot_nodes=slot_nodes)
+        return _histogram_fm(bins, slot, stats, nslots, B, prep, tro=tro, slot_nodes=slot_nodes)
     hist = torch.zeros((nslots, F, B, S), dtype=torch.float32, device=bins.device)
     if n == 0 or nslots == 0:
         return hist
-    rc = L.alink_tree_hist_f32(bins.data_ptr(), n, F, slot.data_ptr(), stats.data_ptr(), S, B, nslots,
-                               hist.data_ptr(), _num_cus(bins.device),
-                               HIST_VARIANT if variant is None else int(variant), _lib.stream_ptr(bins.device))
-    if rc != 0:
-        raise RuntimeError(f"alink_tree_hist_f32 failed: {rc}")
+    _lib.call("alink_tree_hist_f32", bins.data_ptr(), n, F, slot.data_ptr(), stats.data_ptr(), S, B, nslots,
+              hist.data_ptr(), _num_cus(bins.device), HIST_VARIANT if variant is None else int(variant),
+              _lib.stream_ptr(bins.device))
     return hist
 
 
@@ -333,11 +324,8 @@ def route_torch(bins, node, feat, base, route_tab):
 def route(bins: torch.Tensor, node: torch.Tensor, feat: torch.Tensor, base: torch.Tensor,
           route_tab: torch.Tensor) -> torch.Tensor:
     """New int32 node ids (in place on GPU)."""
-    if not bins.is_cuda:
+    if not bins.is_cuda or not _lib.kernels_enabled():
         return route_torch(bins, node, feat, base, route_tab)
-    if not _lib.available() and _lib.torch_fallback_allowed():
-        return route_torch(bins, node, feat, base, route_tab)
-    L = _lib.require()
     n, F = bins.shape
     nn = feat.shape[0]
     if route_tab.shape != (nn, 256):
@@ -348,10 +336,8 @@ def route(bins: torch.Tensor, node: torch.Tensor, feat: torch.Tensor, base: torc
     base = base.to(torch.int32).contiguous()
     route_tab = route_tab.to(torch.int16).contiguous()
     assert node.dtype == torch.int32 and node.is_contiguous() and node.shape[0] == n
-    rc = L.alink_tree_route(bins.data_ptr(), n, F, node.data_ptr(), feat.data_ptr(), base.data_ptr(),
-                            route_tab.data_ptr(), nn, _num_cus(bins.device), _lib.stream_ptr(bins.device))
-    if rc != 0:
-        raise RuntimeError(f"alink_tree_route failed: {rc}")
+    _lib.call("alink_tree_route", bins.data_ptr(), n, F, node.data_ptr(), feat.data_ptr(), base.data_ptr(),
+              route_tab.data_ptr(), nn, _num_cus(bins.device), _lib.stream_ptr(bins.device))
     return node
 
 
@@ -369,18 +355,15 @@ def node_sums_torch(node: torch.Tensor, sample: torch.Tensor, stats: torch.Tenso
 
 def node_sums(node: torch.Tensor, sample: torch.Tensor, stats: torch.Tensor, nnodes: int) -> torch.Tensor:
     """[nnodes, S] fp64 sums of ``stats`` rows per node id (sampled rows only) — node counters."""
-    if not stats.is_cuda or (not _lib.available() and _lib.torch_fallback_allowed()):
+    if not stats.is_cuda or not _lib.kernels_enabled():
         return node_sums_torch(node, sample, stats, nnodes)
-    L = _lib.require()
     n, S = stats.shape
     node = node.to(torch.int32).contiguous()
     samp = sample.to(torch.uint8).contiguous()
     st = stats.to(torch.float32).contiguous()
     out = torch.zeros((max(nnodes, 1), S), dtype=torch.float64, device=stats.device)
-    rc = L.alink_tree_node_sums(node.data_ptr(), samp.data_ptr(), st.data_ptr(), n, S, nnodes, out.data_ptr(),
-                                _num_cus(stats.device), _lib.stream_ptr(stats.device))
-    if rc != 0:
-        raise RuntimeError(f"alink_tree_node_sums failed: {rc}")
+    _lib.call("alink_tree_node_sums", node.data_ptr(), samp.data_ptr(), st.data_ptr(), n, S, nnodes, out.data_ptr(),
+              _num_cus(stats.device), _lib.stream_ptr(stats.device))
     return out[:nnodes]
 
 
@@ -398,7 +381,7 @@ def f32_threshold_table(thresholds, TP: int) -> np.ndarray:
     return tab
 
 
-def _quantize_f32(L, cols, nulls, thresholds, out_cols, n, F, missing, out):
+def _quantize_f32(cols, nulls, thresholds, out_cols, n, F, missing, out):
     dev = out.device
     T = max(1, max(len(t) for t in thresholds))
     TP = 1
@@ -410,10 +393,8 @@ def _quantize_f32(L, cols, nulls, thresholds, out_cols, n, F, missing, out):
                         dtype=torch.int64).to(dev)
     oc = torch.tensor(list(out_cols), dtype=torch.int32).to(dev)
     thr = torch.from_numpy(f32_threshold_table(thresholds, TP)).to(dev)
-    rc = L.alink_tree_quantize_f32(meta[0].data_ptr(), meta[1].data_ptr(), oc.data_ptr(), len(cols), n, F,
-                                   thr.data_ptr(), TP, int(missing), out.data_ptr(), _lib.stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"alink_tree_quantize_f32 failed: {rc}")
+    _lib.call("alink_tree_quantize_f32", meta[0].data_ptr(), meta[1].data_ptr(), oc.data_ptr(), len(cols), n, F,
+              thr.data_ptr(), TP, int(missing), out.data_ptr(), _lib.stream_ptr(dev))
     torch.cuda.current_stream(dev).synchronize()      # the pointer tables must outlive the kernel
 
 
@@ -421,7 +402,7 @@ def quantize(cols, nulls, thresholds, out_cols, n: int, F: int, missing: int, ou
     """K5: bin continuous columns into ``out`` (uint8 [n, F], row-major) on the GPU.  ``cols`` fp32/fp64 device
     vectors [n], ``nulls`` bool masks or None, ``thresholds`` per column (ascending fp64 numpy), ``out_cols``
     destination column per input (``bin = #thresholds < x``; NaN / null -> ``missing``)."""
-    L = _lib.require()
+    _lib.require()
     dev = out.device
     Fc = len(cols)
     if Fc == 0 or n == 0:
@@ -430,7 +411,7 @@ def quantize(cols, nulls, thresholds, out_cols, n: int, F: int, missing: int, ou
     f32 = [i for i, c in enumerate(cols) if c.dtype == torch.float32]
     if f32:
         # fp32 columns: exact fp32 threshold tables, half the LDS traffic of the fp64 search (quantize_f32)
-        _quantize_f32(L, [cols[i] for i in f32], [nulls[i] for i in f32], [thresholds[i] for i in f32],
+        _quantize_f32([cols[i] for i in f32], [nulls[i] for i in f32], [thresholds[i] for i in f32],
                       [out_cols[i] for i in f32], n, F, missing, out)
         rest = [i for i in range(Fc) if cols[i].dtype != torch.float32]
         if not rest:
@@ -451,25 +432,20 @@ def quantize(cols, nulls, thresholds, out_cols, n: int, F: int, missing: int, ou
     oc = torch.tensor(list(out_cols), dtype=torch.int32).to(dev)
     nt = torch.tensor([len(t) for t in thresholds], dtype=torch.int32).to(dev)
     thr = thr.to(dev)
-    rc = L.alink_tree_quantize(meta[0].data_ptr(), meta[1].data_ptr(), is32.data_ptr(), oc.data_ptr(), Fc, n, F,
-                               thr.data_ptr(), nt.data_ptr(), T, int(missing), out.data_ptr(), _lib.stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"alink_tree_quantize failed: {rc}")
+    _lib.call("alink_tree_quantize", meta[0].data_ptr(), meta[1].data_ptr(), is32.data_ptr(), oc.data_ptr(), Fc, n, F,
+              thr.data_ptr(), nt.data_ptr(), T, int(missing), out.data_ptr(), _lib.stream_ptr(dev))
     # keep the pointer tables alive until the kernel has consumed them
     torch.cuda.current_stream(dev).synchronize()
 
 
 def gbdt_split(H: torch.Tensor, min_leaf: float, min_hess: float, gi: int = 1, hi: int = 2, ci: int = 3):
     """K8: (best gain [m, F] fp64, best bin [m, F] int64) of the GBDT gain over the fp32 histogram H [m,F,B,S]."""
-    L = _lib.require()
     m, F, B, S = H.shape
     H = H.to(torch.float32).contiguous()
     gain = torch.empty((m, F), dtype=torch.float64, device=H.device)
     binj = torch.empty((m, F), dtype=torch.int32, device=H.device)
-    rc = L.alink_gbdt_split(H.data_ptr(), m, F, B, S, gi, hi, ci, float(min_leaf), float(min_hess),
-                            gain.data_ptr(), binj.data_ptr(), _lib.stream_ptr(H.device))
-    if rc != 0:
-        raise RuntimeError(f"alink_gbdt_split failed: {rc}")
+    _lib.call("alink_gbdt_split", H.data_ptr(), m, F, B, S, gi, hi, ci, float(min_leaf), float(min_hess),
+              gain.data_ptr(), binj.data_ptr(), _lib.stream_ptr(H.device))
     return gain, binj.to(torch.int64)
 
 
@@ -485,19 +461,14 @@ def tree_split(H: torch.Tensor, kind: str, is_cat: torch.Tensor, n_classes: int,
     m, F, B, S = H.shape
     if S not in SPLIT_S or B > 257:
         return None
-    L = _lib.require()
     H = H.to(torch.float32).contiguous()
     cat = is_cat.to(device=H.device, dtype=torch.uint8).contiguous()
     gain = torch.empty((m, F), dtype=torch.float64, device=H.device)
     pos = torch.empty((m, F), dtype=torch.int32, device=H.device)
-    rc = L.alink_tree_split(H.data_ptr(), m, F, B, S, _CRIT[kind], int(n_classes), cat.data_ptr(), float(min_leaf),
-                            float(min_hess), float(min_ratio), float(min_gain), gain.data_ptr(), pos.data_ptr(),
-                            _lib.stream_ptr(H.device))
-    if rc == 3:
-        return None
-    if rc != 0:
-        raise RuntimeError(f"alink_tree_split failed: {rc}")
-    return gain, pos.to(torch.int64)
+    rc = _lib.call("alink_tree_split", H.data_ptr(), m, F, B, S, _CRIT[kind], int(n_classes), cat.data_ptr(),
+                   float(min_leaf), float(min_hess), float(min_ratio), float(min_gain), gain.data_ptr(),
+                   pos.data_ptr(), _lib.stream_ptr(H.device), accept=(3,))       # 3: shape not covered
+    return None if rc == 3 else (gain, pos.to(torch.int64))
 
 
 def split_order_key(h, kind: str, n_classes: int, categorical: bool):

@@ -17,8 +17,7 @@ __all__ = ["kernel_supported", "HuffmanDevice", "sg_hs_train"]
 
 
 def kernel_supported(dev, d: int) -> bool:
-    return torch.device(dev).type == "cuda" and 1 <= d <= 512 and \
-        (_lib.available() or not _lib.torch_fallback_allowed())
+    return torch.device(dev).type == "cuda" and 1 <= d <= 512 and _lib.kernels_enabled()
 
 
 class HuffmanDevice:
@@ -33,7 +32,7 @@ class HuffmanDevice:
 
 def sg_hs_train(docs: List[np.ndarray], shrinks: List[np.ndarray], window: int, H: HuffmanDevice,
                 syn0: torch.Tensor, syn1: torch.Tensor, alpha: float, max_waves: int = 0) -> None:
-    L = _lib.require()
+    _lib.require()
     keep = [(d, b) for d, b in zip(docs, shrinks) if len(d) >= 2]
     if not keep:
         return
@@ -45,9 +44,6 @@ def sg_hs_train(docs: List[np.ndarray], shrinks: List[np.ndarray], window: int, 
     dend = np.repeat(starts + lens, lens).astype(np.int32)
     dev = syn0.device
     t = [torch.as_tensor(a, device=dev) for a in (tok, dstart, dend, shr)]
-    rc = L.alink_w2v_sg_hs_f32(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), int(tok.size),
-                               int(window), H.codes.data_ptr(), H.points.data_ptr(), H.lens.data_ptr(), H.Lmax,
-                               syn0.data_ptr(), syn1.data_ptr(), int(syn0.shape[1]), float(alpha), int(max_waves),
-                               _lib.stream_ptr(dev))
-    if rc != 0:
-        raise RuntimeError(f"alink_w2v_sg_hs_f32 failed: {rc}")
+    _lib.call("alink_w2v_sg_hs_f32", t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), int(tok.size),
+              int(window), H.codes.data_ptr(), H.points.data_ptr(), H.lens.data_ptr(), H.Lmax, syn0.data_ptr(),
+              syn1.data_ptr(), int(syn0.shape[1]), float(alpha), int(max_waves), _lib.stream_ptr(dev))

@@ -46,22 +46,6 @@ _DT = {torch.float32: 0, torch.float64: 1}
 _OP = {"sum": 0, "max": 1, "min": 2}
 
 
-def _sigs(L):
-    c_vp, c_i64, c_int = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
-    L.alink_ar_alloc.argtypes = [c_i64, ctypes.POINTER(c_vp)]
-    L.alink_ar_ipc_handle.argtypes = [c_vp, c_vp]
-    L.alink_ar_ipc_open.argtypes = [c_vp, ctypes.POINTER(c_vp)]
-    L.alink_ar_ipc_close.argtypes = [c_vp]
-    L.alink_ar_free.argtypes = [c_vp]
-    L.alink_oneshot_allreduce.argtypes = [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, ctypes.c_uint32, c_vp, c_vp,
-                                          c_i64, c_int, c_int, ctypes.c_double, c_vp, c_vp, c_vp]
-    L.alink_ar_host_word_alloc.argtypes = [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)]
-    L.alink_ar_host_word_free.argtypes = [c_vp]
-    for f in ("alink_ar_alloc", "alink_ar_ipc_handle", "alink_ar_ipc_open", "alink_ar_ipc_close", "alink_ar_free",
-              "alink_oneshot_allreduce", "alink_ar_handle_size", "alink_ar_host_word_alloc", "alink_ar_host_word_free"):
-        getattr(L, f).restype = c_int
-
-
 class OneShot:
     """Staging buffers + peer tables for ``P`` ranks.  ``bases[p]`` are device addresses valid in this process
     (IPC-opened for peers, own allocation for ``rank``); a single process may also pass P local allocations
@@ -69,8 +53,7 @@ class OneShot:
 
     def __init__(self, device, P: int, rank: int, cap_bytes: int, bases: List[int], owned: List[int],
                  opened: List[int]):
-        self.L = _lib.require()
-        _sigs(self.L)
+        _lib.require()
         self.device, self.P, self.rank, self.cap = device, P, rank, int(cap_bytes)
         self.owned, self.opened = owned, opened
         self.flag_off = 2 * self.cap
@@ -80,7 +63,7 @@ class OneShot:
         # the kernel also sets a mapped host word on a timeout, so the per-call check is a host read (no copy)
         self._hword, self._hword_dev, self._hview = None, None, None
         h, d = ctypes.c_void_p(), ctypes.c_void_p()
-        if self.L.alink_ar_host_word_alloc(ctypes.byref(h), ctypes.byref(d)) == 0 and d.value:
+        if _lib.query("alink_ar_host_word_alloc", ctypes.byref(h), ctypes.byref(d)) == 0 and d.value:
             import numpy as np
             self._hword, self._hword_dev = h.value, d.value
             self._hview = np.ctypeslib.as_array((ctypes.c_int32 * 1).from_address(h.value))
@@ -95,12 +78,8 @@ class OneShot:
 
     @staticmethod
     def alloc(cap_bytes: int, P: int) -> int:
-        L = _lib.require()
-        _sigs(L)
         p = ctypes.c_void_p()
-        rc = L.alink_ar_alloc(OneShot.region_bytes(cap_bytes, P), ctypes.byref(p))
-        if rc != 0:
-            raise RuntimeError(f"alink_ar_alloc failed: {rc}")
+        _lib.call("alink_ar_alloc", OneShot.region_bytes(cap_bytes, P), ctypes.byref(p))
         return int(p.value)
 
     def launch(self, t: torch.Tensor, out: torch.Tensor, op: str = "sum", rank: Optional[int] = None,
@@ -114,13 +93,10 @@ class OneShot:
         from ..utils import trace as _trace
         tmo = TIMEOUT_S if timeout_s is None else float(timeout_s)
         with _trace.span("oneshot_allreduce", "kernel", device=True, bytes=int(n * t.element_size()), P=self.P):
-            rc = self.L.alink_oneshot_allreduce(t.data_ptr(), out.data_ptr(), n, _DT[t.dtype], _OP[op], self.P,
-                                                self.rank if rank is None else rank, seq & 0xFFFFFFFF,
-                                                self.peer_data.data_ptr(), self.peer_flags.data_ptr(), self.cap,
-                                                BLOCKS, phases, tmo, self.err.data_ptr(), self._hword_dev,
-                                                _lib.stream_ptr(self.device))
-        if rc != 0:
-            raise RuntimeError(f"alink_oneshot_allreduce failed: {rc}")
+            _lib.call("alink_oneshot_allreduce", t.data_ptr(), out.data_ptr(), n, _DT[t.dtype], _OP[op], self.P,
+                      self.rank if rank is None else rank, seq & 0xFFFFFFFF, self.peer_data.data_ptr(),
+                      self.peer_flags.data_ptr(), self.cap, BLOCKS, phases, tmo, self.err.data_ptr(),
+                      self._hword_dev, _lib.stream_ptr(self.device))
         self.calls += 1
         return out
 
@@ -165,12 +141,12 @@ class OneShot:
     def close(self):
         if self._hword is not None:
             self._hview = None
-            self.L.alink_ar_host_word_free(ctypes.c_void_p(self._hword))
+            _lib.query("alink_ar_host_word_free", self._hword)
             self._hword, self._hword_dev = None, None
         for p in self.opened:
-            self.L.alink_ar_ipc_close(ctypes.c_void_p(p))
+            _lib.query("alink_ar_ipc_close", p)
         for p in self.owned:
-            self.L.alink_ar_free(ctypes.c_void_p(p))
+            _lib.query("alink_ar_free", p)
         self.opened, self.owned = [], []
 
 
@@ -221,16 +197,10 @@ def get() -> Optional[OneShot]:
     dev = comm.device_for_rank()
     ok, inst, base, opened = 1.0, None, None, []
     handles = None
-    L = None
     try:
-        L = _lib.require()
-        _sigs(L)
         base = OneShot.alloc(MAX_BYTES, P)
-        hs = int(L.alink_ar_handle_size())
-        buf = ctypes.create_string_buffer(hs)
-        rc = L.alink_ar_ipc_handle(ctypes.c_void_p(base), buf)
-        if rc != 0:
-            raise RuntimeError(f"hipIpcGetMemHandle failed: {rc}")
+        buf = ctypes.create_string_buffer(_lib.query("alink_ar_handle_size"))
+        _lib.call("alink_ar_ipc_handle", base, buf)
         mine = bytes(buf.raw)
     except Exception as e:
         ok, mine = 0.0, b""
@@ -246,9 +216,8 @@ def get() -> Optional[OneShot]:
                 if not handles[p]:
                     raise RuntimeError("peer has no handle")
                 q = ctypes.c_void_p()
-                rc = L.alink_ar_ipc_open(ctypes.create_string_buffer(handles[p], len(handles[p])), ctypes.byref(q))
-                if rc != 0:
-                    raise RuntimeError(f"hipIpcOpenMemHandle failed: {rc}")
+                _lib.call("alink_ar_ipc_open", ctypes.create_string_buffer(handles[p], len(handles[p])),
+                          ctypes.byref(q))
                 opened.append(int(q.value))
                 bases.append(int(q.value))
             inst = OneShot(dev, P, rank, MAX_BYTES, bases, [base], opened)
@@ -261,9 +230,9 @@ def get() -> Optional[OneShot]:
             inst.close()
         else:                       # failure paths: release what this rank did allocate / open
             for q in opened:
-                L.alink_ar_ipc_close(ctypes.c_void_p(q))
+                _lib.query("alink_ar_ipc_close", q)
             if base is not None:
-                L.alink_ar_free(ctypes.c_void_p(base))
+                _lib.query("alink_ar_free", base)
         return None
     # validate on a probe buffer: the exact rank-order sum every rank can compute locally (integers in fp64)
     probe = torch.arange(1000, dtype=torch.float64, device=dev) * (rank + 1) + 0.25

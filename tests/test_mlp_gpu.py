@@ -14,15 +14,15 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("n,K", [(1, 2), (5000, 3), (70001, 10), (999, 32)])
 def test_softmax_full_grad_matches_torch(n, K):
-    L = _lib.require()
+    _lib.require()
     g = torch.Generator(device="cuda").manual_seed(n + K)
     z = torch.randn(n, K, device="cuda", dtype=torch.float64, generator=g) * 4
     y = torch.randint(0, K, (n,), device="cuda", generator=g).double()
     w = torch.rand(n, device="cuda", dtype=torch.float64, generator=g) + 0.5
     R = torch.empty_like(z)
-    part = torch.zeros(L.alink_softmax_grid(n), dtype=torch.float64, device="cuda")
-    assert L.alink_softmax_full_grad_f64(z.data_ptr(), y.data_ptr(), w.data_ptr(), n, K, R.data_ptr(),
-                                         part.data_ptr(), _lib.stream_ptr()) == 0
+    part = torch.zeros(_lib.query("alink_softmax_grid", n), dtype=torch.float64, device="cuda")
+    assert _lib.call("alink_softmax_full_grad_f64", z.data_ptr(), y.data_ptr(), w.data_ptr(), n, K, R.data_ptr(),
+                     part.data_ptr(), _lib.stream_ptr()) == 0
     R0, loss0 = S.softmax_full_grad_torch(z, y, w)
     torch.testing.assert_close(R, R0, rtol=1e-12, atol=1e-13)
     np.testing.assert_allclose(float(part.sum()), float(loss0), rtol=1e-12)

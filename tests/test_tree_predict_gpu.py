@@ -215,17 +215,17 @@ def test_tree_split_predict_kernel_bit_identical_to_one_wave(missing, nd_classes
         x[torch.rand(n) < missing] = float("nan")
         cols[f] = x.cuda()
     codes = dfo.codes(cols, {}, n)
-    L = _lib.require()
+    _lib.require()
     out = {}
     for v in ("1", "2"):
         monkeypatch.setenv("ALINK_TREE_PREDICT_KERNEL", v)
         acc = torch.full((n, dfo.nd), 7.0, dtype=torch.float64, device="cuda")
         wacc = torch.full((n,), 7.0, dtype=torch.float64, device="cuda")
         err = torch.zeros(1, dtype=torch.int32, device="cuda")
-        assert L.alink_tree_predict(codes.data_ptr(), n, dfo.stride, dfo.code_bytes, dfo.nodes.data_ptr(),
-                                    dfo.dist.data_ptr(), dfo.nd, dfo.wsum.data_ptr(), dfo.cat.data_ptr(),
-                                    int(dfo.cat.shape[1]), dfo.roots.data_ptr(), int(dfo.roots.numel()),
-                                    acc.data_ptr(), wacc.data_ptr(), err.data_ptr(), _lib.stream_ptr("cuda:0")) == 0
+        assert _lib.call("alink_tree_predict", codes.data_ptr(), n, dfo.stride, dfo.code_bytes, dfo.nodes.data_ptr(),
+                         dfo.dist.data_ptr(), dfo.nd, dfo.wsum.data_ptr(), dfo.cat.data_ptr(),
+                         int(dfo.cat.shape[1]), dfo.roots.data_ptr(), int(dfo.roots.numel()),
+                         acc.data_ptr(), wacc.data_ptr(), err.data_ptr(), _lib.stream_ptr("cuda:0")) == 0
         torch.cuda.synchronize()
         assert int(err.item()) == 0
         out[v] = (acc.cpu(), wacc.cpu())

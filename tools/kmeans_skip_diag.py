@@ -31,7 +31,7 @@ def main():
     lab = torch.randint(0, k, (n,), generator=g)
     X = (centers[lab] + torch.randn(n, 128, generator=g)).to(dev, torch.bfloat16)
     C = (centers + 0.3 * torch.randn(k, 128, generator=g)).to(dev, torch.float64)
-    grid = int(K._lib.require().alink_kmeans_v10_grid(n, K._num_cus(dev)))
+    grid = K._lib.query("alink_kmeans_v10_grid", n, K._num_cus(dev))
     # the round-5 allocation: uninitialised slabs
     K._BUF.clear()
     K._BUF[(0, grid)] = (torch.empty((grid, K.HIP_KMAX, K.HIP_D), dtype=torch.float32, device=dev),
