@@ -1,6 +1,7 @@
 // java.util.Random (48-bit LCG) batch shuffles for the host runtime: the per-node feature shuffles of
 // seriestree/DecisionTree.bagging (reference A/operator/common/tree/seriestree/DecisionTree.java), the same draws
 // as common/jrandom.py JavaRandom.shuffle, for a whole tree level in one call instead of ~F Python calls per node.
+#include <cmath>
 #include <cstdint>
 
 namespace {
@@ -23,6 +24,12 @@ inline int32_t next_int(uint64_t& seed, int32_t bound) {
     }
 }
 
+// nextDouble: ((next(26) << 27) + next(27)) * 2^-53
+inline double next_double(uint64_t& seed) {
+    const int64_t hi = next_bits(seed, 26), lo = next_bits(seed, 27);
+    return (double)((hi << 27) + lo) * (1.0 / (double)(1LL << 53));
+}
+
 }  // namespace
 
 extern "C" {
@@ -42,6 +49,35 @@ void alink_java_shuffle_rows(uint64_t* seed, int32_t* rows, int64_t m, int32_t n
         }
     }
     *seed = s;
+}
+
+// The next n values of nextGaussian (Marsaglia polar method, as common/jrandom.py JavaRandom.nextGaussian: the same
+// libm log and sqrt, the same operation order), continuing the state *seed and the cached second value
+// (*have_next, *next), and leaving both as n single calls would.
+void alink_java_next_gaussians(uint64_t* seed, int32_t* have_next, double* next, double* out, int64_t n) {
+    uint64_t s = *seed;
+    int32_t have = *have_next;
+    double cached = *next;
+    for (int64_t i = 0; i < n; ++i) {
+        if (have) {
+            out[i] = cached;
+            have = 0;
+            continue;
+        }
+        double v1, v2, q;
+        do {
+            v1 = 2 * next_double(s) - 1;
+            v2 = 2 * next_double(s) - 1;
+            q = v1 * v1 + v2 * v2;
+        } while (!(0 < q && q < 1));
+        const double mul = std::sqrt(-2 * std::log(q) / q);
+        cached = v2 * mul;
+        have = 1;
+        out[i] = v1 * mul;
+    }
+    *seed = s;
+    *have_next = have;
+    *next = cached;
 }
 
 }  // extern "C"

@@ -82,6 +82,29 @@ class JavaRandom:
         self._next_gaussian = v2 * mul
         return v1 * mul
 
+    def nextGaussians(self, n: int) -> "np.ndarray":
+        """The next ``n`` values of ``nextGaussian`` as a float64 array, bit for bit, the cached second value
+        included on both ends — one host C++ call (``_native/csrc/jrandom.cpp``); the Python loop without the
+        library."""
+        import ctypes
+        import numpy as np
+        from .. import _native
+        n = max(int(n), 0)
+        out = np.empty(n, dtype=np.float64)
+        L = _native.lib
+        if L is not None and hasattr(L, "alink_java_next_gaussians") and n:
+            st = ctypes.c_uint64(self._seed)
+            have = ctypes.c_int32(self._next_gaussian is not None)
+            nxt = ctypes.c_double(self._next_gaussian if self._next_gaussian is not None else 0.0)
+            L.alink_java_next_gaussians(ctypes.byref(st), ctypes.byref(have), ctypes.byref(nxt),
+                                        out.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(n))
+            self._seed = int(st.value)
+            self._next_gaussian = float(nxt.value) if have.value else None
+            return out
+        for i in range(n):
+            out[i] = self.nextGaussian()
+        return out
+
     def nextBoolean(self) -> bool:
         return self._next(1) != 0
 

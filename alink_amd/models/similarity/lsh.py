@@ -10,6 +10,10 @@ offsets ``nextDouble()*w`` :21-38; join = equal (table, bucket) candidates, exac
 MI355X-first: the projections of all rows onto all ``numHashTables x numProjectionsPerTable`` directions are
 ONE GEMM on the device; candidate pairs are formed by a bucket hash join on the host-side int keys and their
 exact distances are evaluated in one batched gather + reduction on the device.
+
+That is the host path: the CPU path and the oracle.  On a GPU the operators take ``approx_similarity_join_columns``
+/ ``approx_nearest_neighbors_columns`` below, which hash, join and measure whole column blocks through the kernels of
+``ops/lsh.py`` (``ops/csrc/lsh.hip``) with the hash functions of the same classes, and never densify a sparse row.
 """
 from __future__ import annotations
 
@@ -23,7 +27,8 @@ from ...common.jrandom import JavaRandom
 from ...common.linalg import DenseVector, SparseVector, VectorUtil
 
 __all__ = ["murmur3_32_words", "MinHashLSH", "BucketRandomProjectionLSH", "approx_similarity_join",
-           "approx_nearest_neighbors", "jaccard_distance_sets"]
+           "approx_nearest_neighbors", "jaccard_distance_sets", "approx_similarity_join_columns",
+           "approx_nearest_neighbors_columns"]
 
 HASH_PRIME = 2038074743
 _M32 = np.uint64(0xFFFFFFFF)
@@ -147,7 +152,7 @@ class BucketRandomProjectionLSH:
         self.r = np.zeros((num_tables, num_proj))
         for i in range(num_tables):
             for j in range(num_proj):
-                d = np.asarray([rnd.nextGaussian() for _ in range(vector_size)])
+                d = rnd.nextGaussians(vector_size)
                 nrm = np.linalg.norm(d)
                 self.R[i, j] = d / nrm if nrm > 0 else d
                 self.r[i, j] = rnd.nextDouble() * self.width
@@ -205,6 +210,67 @@ def approx_similarity_join(left_vecs, right_vecs, distance_type, seed, num_proj,
     d = dist(L, ai, R, bi)
     keep = d < threshold
     return list(zip(ai[keep].tolist(), bi[keep].tolist(), d[keep].tolist()))
+
+
+def _device_pairs(a_fm, b_fm, distance_type: str, seed, num_proj, num_tables, width, vector_size):
+    """Candidate pairs of two ``FeatureMatrix`` column blocks on a GPU and their exact distances, through the
+    kernels of ``ops/lsh.py`` (rows are never densified): ``(ai, bi, dist)`` sorted by (a, b), or None when a side
+    is not device-eligible (``canonical_csr``) and the caller takes the host path.  The hash functions are the host
+    classes' own (same seeds, coefficients and directions)."""
+    from ...ops import lsh as K
+    dev = a_fm.device
+    T, P = int(num_tables), int(num_proj)
+    empty = torch.zeros(0, dtype=torch.int64, device=dev)
+    if distance_type.upper() == "JACCARD":
+        A, B = K.canonical_csr(a_fm), K.canonical_csr(b_fm)
+        if A is None or B is None:
+            return None
+        if A.nrows == 0 or B.nrows == 0:
+            return empty, empty.clone(), torch.zeros(0, dtype=torch.float64, device=dev)
+        lsh = MinHashLSH(seed, P, T)
+        ai, bi = K.candidate_pairs(K.minhash_tables(A, lsh.A, lsh.B), K.minhash_tables(B, lsh.A, lsh.B))
+        return ai, bi, K.pair_jaccard(A, B, ai, bi)
+    if a_fm.is_sparse or b_fm.is_sparse:
+        A, B = K.canonical_csr(a_fm), K.canonical_csr(b_fm)
+        if A is None or B is None:
+            return None
+    else:
+        d = max(a_fm.ncols, b_fm.ncols, 1)
+        A = a_fm.to_dense(d).to(torch.float64).contiguous()
+        B = b_fm.to_dense(d).to(torch.float64).contiguous()
+    if a_fm.nrows == 0 or b_fm.nrows == 0:
+        return empty, empty.clone(), torch.zeros(0, dtype=torch.float64, device=dev)
+    lsh = BucketRandomProjectionLSH(seed, int(vector_size), P, T, width)
+    d = int(vector_size)
+    Rt = np.zeros((max(d, a_fm.ncols, b_fm.ncols), T * P))      # columns past the directions' size project to 0
+    Rt[:d] = lsh.R.reshape(T * P, d).T
+    Rt = torch.as_tensor(Rt, device=dev)
+    ha, hb = (K.brp_tables(fm.mm(Rt).contiguous(), lsh.r, lsh.width, T) for fm in (a_fm, b_fm))
+    ai, bi = K.candidate_pairs(ha, hb)
+    return ai, bi, K.pair_euclidean(A, B, ai, bi)
+
+
+def approx_similarity_join_columns(left_fm, right_fm, distance_type, seed, num_proj, num_tables, width, threshold):
+    """``approx_similarity_join`` on the device for two ``FeatureMatrix`` blocks: ``(ai, bi, dist)`` tensors of the
+    pairs with ``dist < threshold``, sorted by (left, right) index; None when a side is not device-eligible."""
+    res = _device_pairs(left_fm, right_fm, distance_type, seed, num_proj, num_tables, width, left_fm.ncols)
+    if res is None:
+        return None
+    ai, bi, d = res
+    keep = d < threshold
+    return ai[keep], bi[keep], d[keep]
+
+
+def approx_nearest_neighbors_columns(query_fm, dict_fm, distance_type, seed, num_proj, num_tables, width, top_n,
+                                     basis_size):
+    """``approx_nearest_neighbors`` on the device: ``(qi, di, dist, rank)`` tensors by query, then rank from 1;
+    ``basis_size`` is the vector size of the LSH basis (the directions' size).  None when a side is not
+    device-eligible."""
+    from ...ops import lsh as K
+    res = _device_pairs(query_fm, dict_fm, distance_type, seed, num_proj, num_tables, width, basis_size)
+    if res is None:
+        return None
+    return K.top_n(*res, top_n)
 
 
 def approx_nearest_neighbors(query_vecs, dict_vecs, distance_type, seed, num_proj, num_tables, width, top_n,

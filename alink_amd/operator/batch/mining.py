@@ -15,6 +15,7 @@ from ...common.types import TableSchema, Types
 from ...models.associationrule import mining as M
 from ...models.outlier.sos import sos_scores
 from ...models.similarity import lsh as L
+from ...ops import lsh as K
 from ...parallel import comm
 from ..base import BatchOperator, gather_table, partition_bounds
 
@@ -120,12 +121,39 @@ def _lsh_args(p):
             int(p.get("numHashTables")), float(p.get("projectionWidth")))
 
 
+def _own_columns(schema, cols, env):
+    """``_own_block`` for an output that is already columns (the device path: no per-row Python tuples)."""
+    mt = MTable(schema, cols)
+    if comm.get_world_size() > 1:
+        lo, hi = partition_bounds(mt.num_rows, env)
+        mt = mt.slice(lo, hi)
+    return mt
+
+
+def _lsh_columns(table, col, device):
+    from ...models.common.features import extract_features
+    return extract_features(table, None, col, device)
+
+
 class ApproxVectorSimilarityJoinLSHBatchOp(BatchOperator):
     def linkFrom(self, *inputs):
         self.checkOpSize(2, inputs)
         p = self.resolvedParams()
         left, right = gather_table(inputs[0].getOutputTable()), gather_table(inputs[1].getOutputTable())
         lid, rid = p.get("leftIdCol"), p.get("rightIdCol")
+        if K.device_selected(self.env.device):
+            dev = self.env.device
+            res = L.approx_similarity_join_columns(
+                _lsh_columns(left, p.get("leftCol"), dev), _lsh_columns(right, p.get("rightCol"), dev),
+                *_lsh_args(p), float(p.get("distanceThreshold")))
+            if res is not None:         # None: rows that are not device-eligible take the host path below
+                ai, bi, d = res
+                ln, rn = (lid + "_left", rid + "_right") if lid.lower() == rid.lower() else (lid, rid)
+                dcol = p.get("outputCol") if p.contains("outputCol") and p.get("outputCol") else "distance"
+                schema = TableSchema([ln, rn, dcol], [left.col_type(lid), right.col_type(rid), Types.DOUBLE])
+                self.setOutputTable(_own_columns(
+                    schema, [left.col(lid).take(ai), right.col(rid).take(bi), Column(d.cpu())], self.env))
+                return self
         res = L.approx_similarity_join(left.col(p.get("leftCol")).to_list(), right.col(p.get("rightCol")).to_list(),
                                        *_lsh_args(p), float(p.get("distanceThreshold")), self.env.device)
         lids, rids = left.col(lid).to_list(), right.col(rid).to_list()
@@ -143,6 +171,21 @@ class ApproxVectorSimilarityTopNLSHBatchOp(BatchOperator):
         p = self.resolvedParams()
         left, right = gather_table(inputs[0].getOutputTable()), gather_table(inputs[1].getOutputTable())
         lid, rid = p.get("leftIdCol"), p.get("rightIdCol")
+        if K.device_selected(self.env.device):
+            dev = self.env.device
+            dict_fm = _lsh_columns(left, p.get("leftCol"), dev)         # the left table is the dictionary and basis
+            res = L.approx_nearest_neighbors_columns(_lsh_columns(right, p.get("rightCol"), dev), dict_fm,
+                                                     *_lsh_args(p), int(p.get("topN")), dict_fm.ncols)
+            if res is not None:         # None: rows that are not device-eligible take the host path below
+                qi, di, d, rank = res
+                ln, rn = (lid + "_left", rid + "_right") if lid.lower() == rid.lower() else (lid, rid)
+                dcol = p.get("outputCol") if p.contains("outputCol") and p.get("outputCol") else "distance"
+                schema = TableSchema([rn, ln, dcol, "rank"], [right.col_type(rid), left.col_type(lid), Types.DOUBLE,
+                                                             Types.LONG])
+                self.setOutputTable(_own_columns(
+                    schema, [right.col(rid).take(qi), left.col(lid).take(di), Column(d.cpu()),
+                             Column(rank.to(torch.int64).cpu())], self.env))
+                return self
         lv = left.col(p.get("leftCol")).to_list()
         res = L.approx_nearest_neighbors(right.col(p.get("rightCol")).to_list(), lv, *_lsh_args(p),
                                          int(p.get("topN")), self.env.device, lsh_basis_vecs=lv)

@@ -178,6 +178,13 @@ _SIGNATURES = {
                                  _c_int, _c_int, _c_vp],
     "alink_bisect_descend_csr": [_c_vp, _c_vp, _c_int, _c_vp, _c_i64, _c_i64, _c_vp, _c_int, _c_vp, _c_vp, _c_vp,
                                  _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_vp],
+    "alink_lsh_minhash": [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_int, _c_vp],
+    "alink_lsh_brp_hash": [_c_vp, _c_i64, _c_vp, _c_d, _c_int, _c_int, _c_vp, _c_int, _c_vp],
+    "alink_lsh_pair_jaccard": [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_i64,
+                               _c_vp, _c_int, _c_vp],
+    "alink_lsh_pair_euclid_csr": [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp,
+                                  _c_vp, _c_i64, _c_vp, _c_int, _c_vp],
+    "alink_lsh_pair_euclid_f64": [_c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_i64, _c_vp, _c_int, _c_vp],
     "alink_ar_alloc": [_c_i64, ctypes.POINTER(_c_vp)],
     "alink_ar_free": [_c_vp],
     "alink_ar_ipc_handle": [_c_vp, _c_vp],
