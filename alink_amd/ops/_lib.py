@@ -185,6 +185,10 @@ _SIGNATURES = {
     "alink_lsh_pair_euclid_csr": [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp,
                                   _c_vp, _c_i64, _c_vp, _c_int, _c_vp],
     "alink_lsh_pair_euclid_f64": [_c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_i64, _c_vp, _c_int, _c_vp],
+    "alink_evalcluster_rows_f64": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int,
+                                   _c_vp, _c_int, _c_vp],
+    "alink_evalcluster_rows_csr": [_c_vp, _c_vp, _c_int, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int,
+                                   _c_int, _c_vp, _c_int, _c_vp],
     "alink_ar_alloc": [_c_i64, ctypes.POINTER(_c_vp)],
     "alink_ar_free": [_c_vp],
     "alink_ar_ipc_handle": [_c_vp, _c_vp],

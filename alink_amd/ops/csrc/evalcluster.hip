@@ -1,0 +1,443 @@
+// Cluster evaluation row pass (``ops/evalcluster.py``): every row against the k cluster means in one pass over the
+// rows, all arithmetic fp64, no [n, k] buffer.  Output per row r: out[r] = [own, own^2, sil].
+//
+//   own  the distance of the row to the mean of its own cluster cid[r] (dist 0 EUCLIDEAN sqrt(sum (x - m)^2),
+//        1 COSINE 1 - x.m / (|x| |m|), 1 where a norm is 0, 2 CITYBLOCK sum |x - m|);
+//   sil  the closed-form silhouette of ClusterEvaluationUtil.calSilhouetteCoefficient from the dots x.m_j, the
+//        cluster counts cnt_j and squared-norm sums n2_j: EUCLIDEAN dis_j = cnt_j |x|^2 - 2 cnt_j x.m_j + n2_j,
+//        cur = dis_own / (cnt_own - 1), nb = min_{j != own} dis_j / max(cnt_j, 1) (taken as a product with the
+//        reciprocal the wrapper rounded once per cluster: k divisions per row would cost as much as the dots at
+//        small d); otherwise dis_j = 1 - x.m_j,
+//        cur = dis_own cnt_own / (cnt_own - 1), nb = min_{j != own} dis_j; cur = 0 when cnt_own <= 1, nb = +inf
+//        when there is no other cluster; sil = cur < nb ? 1 - cur / nb : nb / cur - 1, NaN -> 0.
+//   A row whose cid is outside [0, k) gets [0, 0, 0] and no mean is read for it.
+//
+// * alink_evalcluster_rows_f64 — dense fp64 rows [n, d], 1 <= d <= 1024.  The k dots are the problem of
+//   dense64_nearest_kernel (kmeans_dense64.hip) and are solved the same way: a workgroup of 4 waves takes 64 rows
+//   (a wave its 16), walks the clusters in blocks of 16 NT and the dims in chunks of 32, and runs
+//   v_mfma_f64_16x16x4_f64 with the mean tile as A and the rows as B; the mean block of a dim chunk is staged in LDS
+//   from the lane-ordered image of ``kmeans_dense64._centroid_image`` (COSINE code: plain dots, accumulators start at
+//   0).  d is zero-padded in the registers; odd d and 8-byte-aligned rows take scalar loads (VEC = false).
+//   The epilogue walks the lane's own 4 NT accumulators (clusters g + 4 q of each tile), then the four lane groups:
+//   a min that skips j == cid and every j >= k, and the own-cluster dot picked out by index.  |x|^2 is summed per
+//   lane in ascending dim order and combined by a fixed xor butterfly (16, 32) before the epilogue.
+//   own comes from the row's registers against a gather of mean[cid] (32 contiguous bytes per lane and 16-dim
+//   group, served by L2: the table is k d doubles), each lane adding in ascending dim order, the same butterfly
+//   across the lane groups: the three outputs depend on the row alone, not on the grid or the row's wave.
+//   Choices: LDS 4 NT KiB per workgroup (<= 32 KiB, so LDS never limits below 5 workgroups per CU); the image is
+//   written in lane order, 32 bytes per lane, so the ds_read_b128 pairs are conflict-free; 256-thread workgroups
+//   so that one staged block serves 64 rows; the grid is capped at 1024 workgroups that stride over the row batches.
+// * alink_evalcluster_rows_csr — CSR rows (int32 / int64 columns), one wave per row, as sparse_nearest_kernel
+//   (kmeans_sparse.hip): the means come transposed and padded, Mt [d, kp], lane l owns clusters l, l + 64, ... of a
+//   block of up to 256 clusters, 64 entries are loaded at a time and walked in stored order with wave-uniform
+//   broadcasts, U gathers in flight; k > 256 loops over cluster blocks.  Entries whose column is outside [0, d)
+//   become (column 0, value 0) before any address is formed and add nothing, to the dots and to the norms alike.
+//   own never touches d elements: with the per-cluster |m|^2 and sum |m| (stat columns 3, 4)
+//     EUCLIDEAN  sqrt(max(0, |m|^2 + sum_nz((x_j - m_j)^2 - m_j^2))),
+//     CITYBLOCK  sum |m| + sum_nz(|x_j - m_j| - |m_j|),
+//     COSINE     1 - x.m / (|x| |m|) from the own dot,
+//   where m_j = Mt[j, cid] is one wave-uniform load per entry.  A row must store a column at most once.
+//   Every lane walks the entries in stored order, so a row's values do not depend on the grid.
+//   Choices: no LDS (the table rows are read once per entry, coalesced over the lanes); 4 rows per 256-thread
+//   workgroup; up to 16384 workgroups striding over the rows.
+// Non-finite rows are not guaranteed (a NaN dot is skipped by the min).  Plain C++ and vector stores only.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace {
+
+typedef double d4_t __attribute__((ext_vector_type(4)));
+typedef double d2_t __attribute__((ext_vector_type(2)));
+
+constexpr int EV_WAVES = 4;          // waves per workgroup
+constexpr int EV_ROWS = 16 * EV_WAVES;
+constexpr int EV_DCH = 32;           // dims per staged chunk (two 16-dim groups u = 0, 1)
+constexpr int EV_NB = 4;             // cluster blocks of 64 a lane of the CSR kernel holds at most
+constexpr int EV_STAT = 8;           // doubles per cluster record: cnt, n2, 1 / max(cnt, 1), |m|^2, sum |m|, padding
+
+__device__ __forceinline__ d4_t mf64(double a, double b, d4_t c) {
+    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+}
+
+__device__ __forceinline__ double bcast_f64(double v, int lane) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+    return __hiloint2double(hi, lo);
+}
+
+__device__ __forceinline__ int64_t bcast_i64(int64_t v, int lane) {
+    const int lo = __builtin_amdgcn_readlane((int)(v & 0xffffffffll), lane);
+    const int hi = __builtin_amdgcn_readlane((int)(v >> 32), lane);
+    return ((int64_t)hi << 32) | (uint32_t)lo;
+}
+
+// dis_j of the closed form from the dot x.m_j
+__device__ __forceinline__ double ev_dis(int dist, double dot, double xn, double cn, double n2) {
+    return dist == 0 ? cn * xn - 2.0 * cn * dot + n2 : 1.0 - dot;
+}
+
+// [own, own^2, sil] of one row from its own distance, its own dis, the neighbour minimum and its cluster's count
+__device__ __forceinline__ void ev_store(double* __restrict__ o, int dist, double own, double disown, double nb,
+                                         double cn) {
+    double cur = 0.0;
+    if (cn > 1.0) cur = dist == 0 ? disown / (cn - 1.0) : disown * cn / (cn - 1.0);
+    double sil = cur < nb ? 1.0 - cur / nb : nb / cur - 1.0;
+    if (sil != sil) sil = 0.0;
+    o[0] = own;
+    o[1] = own * own;
+    o[2] = sil;
+}
+
+// img: per (cluster block, dim chunk) NT * 512 doubles in [u][tile][g][m][step] order; mean [k, d];
+// stat [nblk * 16 NT, 8] = (cnt, n2, 1 / max(cnt, 1), ...), zero on the padded slots.
+// VEC: d is even and X and mean are 16-byte aligned, so a lane's four dims are two aligned 16-byte loads.
+template <int NT, bool VEC>
+__global__ __launch_bounds__(64 * EV_WAVES) void evalcluster_rows_f64_kernel(
+        const double* __restrict__ X, int64_t n, int d, const int* __restrict__ cid, const double* __restrict__ img,
+        const double* __restrict__ mean, const double* __restrict__ stat, int k, int nblk, int ndch, int dist,
+        double* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) double cent[NT * 512];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int m = lane & 15, g = lane >> 4;
+    const int64_t nbatch = (n + EV_ROWS - 1) / EV_ROWS;
+    for (int64_t b = blockIdx.x; b < nbatch; b += gridDim.x) {
+        const int64_t row = b * EV_ROWS + wave * 16 + m;
+        const bool row_ok = row < n;
+        const double* __restrict__ xr = X + (row_ok ? row : 0) * (int64_t)d;
+        const int own = row_ok ? cid[row] : -1;
+        const bool own_ok = own >= 0 && own < k;
+        const double* __restrict__ mr = mean + (own_ok ? own : 0) * (int64_t)d;
+        double nb = __builtin_inf();
+        double owndot = 0.0;            // x . mean[own], on the lane group that holds it
+        double xn = 0.0;
+        double a0 = 0.0, a1 = 0.0;      // own: sum (x - m)^2 | x.m | sum |x - m|;  a1: sum m^2 (COSINE)
+        for (int cb = 0; cb < nblk; ++cb) {
+            d4_t acc[NT];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[t] = d4_t{0.0, 0.0, 0.0, 0.0};
+            xn = 0.0;
+            for (int dc = 0; dc < ndch; ++dc) {
+                // this lane's dims of the row: dc * 32 + 16 u + 4 g + s; outside the row they are zero
+                double xb[2][4];
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const int j0 = dc * EV_DCH + 16 * u + 4 * g;
+                    if (VEC) {
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+                            d2_t v = {0.0, 0.0};
+                            if (row_ok && j0 + 2 * h < d) v = *reinterpret_cast<const d2_t*>(xr + j0 + 2 * h);
+                            xb[u][2 * h] = v[0];
+                            xb[u][2 * h + 1] = v[1];
+                        }
+                    } else {
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) xb[u][s] = (row_ok && j0 + s < d) ? xr[j0 + s] : 0.0;
+                    }
+                }
+                if (cb == 0) {
+                    // the same dims of the row's own mean; the sums run in ascending dim order within the lane
+                    double mb[2][4];
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        const int j0 = dc * EV_DCH + 16 * u + 4 * g;
+                        if (VEC) {
+#pragma unroll
+                            for (int h = 0; h < 2; ++h) {
+                                d2_t v = {0.0, 0.0};
+                                if (own_ok && j0 + 2 * h < d) v = *reinterpret_cast<const d2_t*>(mr + j0 + 2 * h);
+                                mb[u][2 * h] = v[0];
+                                mb[u][2 * h + 1] = v[1];
+                            }
+                        } else {
+#pragma unroll
+                            for (int s = 0; s < 4; ++s) mb[u][s] = (own_ok && j0 + s < d) ? mr[j0 + s] : 0.0;
+                        }
+                    }
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) {
+                            const double x = xb[u][s], mm = mb[u][s];
+                            if (dist == 0) {
+                                const double t = x - mm;
+                                a0 = fma(t, t, a0);
+                            } else if (dist == 1) {
+                                a0 = fma(x, mm, a0);
+                                a1 = fma(mm, mm, a1);
+                            } else {
+                                a0 += fabs(x - mm);
+                            }
+                        }
+                    }
+                }
+                // stage the mean block of this dim chunk: a straight copy of NT * 4 KiB
+                const d2_t* __restrict__ src =
+                    reinterpret_cast<const d2_t*>(img + ((int64_t)cb * ndch + dc) * (NT * 512));
+                __syncthreads();        // the previous chunk's reads are done
+#pragma unroll
+                for (int i = 0; i < NT; ++i)
+                    reinterpret_cast<d2_t*>(cent)[i * 256 + tid] = src[i * 256 + tid];
+                __syncthreads();
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) xn = fma(xb[u][s], xb[u][s], xn);
+#pragma unroll
+                    for (int t0 = 0; t0 < NT; t0 += 4) {
+                        d4_t a[NT < 4 ? NT : 4];
+#pragma unroll
+                        for (int t = 0; t < (NT < 4 ? NT : 4); ++t)
+                            a[t] = *reinterpret_cast<const d4_t*>(cent + (((u * NT + t0 + t) * 4 + g) * 16 + m) * 4);
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) {
+#pragma unroll
+                            for (int t = 0; t < (NT < 4 ? NT : 4); ++t)
+                                acc[t0 + t] = mf64(a[t][s], xb[u][s], acc[t0 + t]);
+                        }
+                    }
+                }
+            }
+            // |x|^2 of the whole row on every lane group: both partners add the same two values
+#pragma unroll
+            for (int o = 16; o < 64; o <<= 1) xn += __shfl_xor(xn, o, 64);
+            // the lane's own clusters: tile, then register
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int c = (cb * NT + t) * 16 + g + 4 * q;
+                    const double dot = acc[t][q];
+                    if (c == own) {
+                        owndot = dot;
+                    } else if (c < k) {
+                        const double* __restrict__ sc = stat + EV_STAT * c;
+                        double v = ev_dis(dist, dot, xn, sc[0], sc[1]);
+                        if (dist == 0) v = v * sc[2];
+                        if (v < nb) nb = v;
+                    }
+                }
+            }
+        }
+        // across the four lane groups of a row (every other group holds owndot = 0)
+#pragma unroll
+        for (int o = 16; o < 64; o <<= 1) {
+            const double ob = __shfl_xor(nb, o, 64);
+            nb = ob < nb ? ob : nb;
+            owndot += __shfl_xor(owndot, o, 64);
+            a0 += __shfl_xor(a0, o, 64);
+            a1 += __shfl_xor(a1, o, 64);
+        }
+        if (g == 0 && row_ok) {
+            double* __restrict__ o = out + row * 3;
+            if (!own_ok) {
+                o[0] = 0.0;
+                o[1] = 0.0;
+                o[2] = 0.0;
+            } else {
+                const double cn = stat[EV_STAT * own], n2 = stat[EV_STAT * own + 1];
+                double ownd;
+                if (dist == 0) {
+                    ownd = sqrt(a0);
+                } else if (dist == 1) {
+                    const double cross = sqrt(xn) * sqrt(a1);
+                    ownd = cross > 0.0 ? 1.0 - a0 / cross : 1.0;
+                } else {
+                    ownd = a0;
+                }
+                ev_store(o, dist, ownd, ev_dis(dist, owndot, xn, cn, n2), nb, cn);
+            }
+        }
+    }
+}
+
+// Mt [d, kp]; stat [kp, 8] = (cnt, n2, 1 / max(cnt, 1), |m|^2, sum |m|, ...), zero on the padded clusters.
+// NB: cluster blocks of 64 per pass (kp >= 64 * NB unless NB == EV_NB, where the tail block is guarded);
+// U: entries whose gathers are issued together.
+template <int NB, int U, typename I>
+__global__ __launch_bounds__(64 * EV_WAVES) void evalcluster_rows_csr_kernel(
+        const int64_t* __restrict__ crow, const I* __restrict__ col, const double* __restrict__ val, int64_t n,
+        int64_t d, const int* __restrict__ cid, const double* __restrict__ Mt, const double* __restrict__ stat, int k,
+        int kp, int dist, double* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t w0 = (int64_t)blockIdx.x * EV_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nw = (int64_t)gridDim.x * EV_WAVES;
+    for (int64_t r = w0; r < n; r += nw) {
+        const int64_t s = crow[r], e = crow[r + 1];
+        const int own = __builtin_amdgcn_readfirstlane(cid[r]);
+        const bool own_ok = own >= 0 && own < k;
+        double* __restrict__ o = out + r * 3;
+        if (!own_ok) {
+            if (lane == 0) {
+                o[0] = 0.0;
+                o[1] = 0.0;
+                o[2] = 0.0;
+            }
+            continue;
+        }
+        const bool rearranged = dist != 1;      // own through the gathered m_j (EUCLIDEAN, CITYBLOCK)
+        double nb = __builtin_inf();
+        double owndot = 0.0;
+        double xn = 0.0;
+        double oacc = 0.0;
+        for (int cb = 0; cb < kp; cb += 64 * NB) {
+            double acc[NB];
+#pragma unroll
+            for (int b = 0; b < NB; ++b) acc[b] = 0.0;
+            xn = 0.0;
+            const bool with_own = rearranged && cb == 0;
+            for (int64_t p = s; p < e; p += 64) {
+                const int m = (int)((e - p) < 64 ? (e - p) : 64);
+                // guarded entry of this lane: an out-of-range column (or a lane past the row) becomes (0, 0.0)
+                int64_t cj = 0;
+                double vj = 0.0;
+                if (lane < m) {
+                    const int64_t c = (int64_t)col[p + lane];
+                    if (c >= 0 && c < d) {
+                        cj = c;
+                        vj = val[p + lane];
+                    }
+                }
+                for (int j0 = 0; j0 < m; j0 += U) {
+                    double v[U];
+                    double mo[U];
+                    double t[U][NB];
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        // lanes j0 + u >= m hold (0, 0.0): they read row 0 of Mt and add nothing
+                        const int j = (j0 + u) & 63;
+                        const int64_t c = bcast_i64(cj, j);
+                        v[u] = bcast_f64(vj, j);
+                        const double* __restrict__ rowp = Mt + c * (int64_t)kp;
+                        mo[u] = with_own ? rowp[own] : 0.0;
+#pragma unroll
+                        for (int b = 0; b < NB; ++b)
+                            t[u][b] = (NB < EV_NB || cb + 64 * b < kp) ? rowp[cb + lane + 64 * b] : 0.0;
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        xn = fma(v[u], v[u], xn);
+                        // a (0, 0.0) entry gives (0 - m)^2 - m^2 = 0 and |0 - m| - |m| = 0 exactly
+                        if (with_own) {     // the first cluster block's walk alone
+                            const double df = v[u] - mo[u];
+                            oacc += dist == 0 ? df * df - mo[u] * mo[u] : fabs(df) - fabs(mo[u]);
+                        }
+#pragma unroll
+                        for (int b = 0; b < NB; ++b) acc[b] = fma(v[u], t[u][b], acc[b]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                const int c = cb + 64 * b + lane;
+                if ((NB < EV_NB || cb + 64 * b < kp) && c < k) {
+                    if (c == own) {
+                        owndot = acc[b];
+                    } else {
+                        const double* __restrict__ sc = stat + EV_STAT * c;
+                        double v = ev_dis(dist, acc[b], xn, sc[0], sc[1]);
+                        if (dist == 0) v = v * sc[2];
+                        if (v < nb) nb = v;
+                    }
+                }
+            }
+        }
+        // over the wave: the minimum, and the own dot from the one lane that holds it (every other lane holds 0)
+#pragma unroll
+        for (int of = 32; of > 0; of >>= 1) {
+            const double ob = __shfl_xor(nb, of, 64);
+            nb = ob < nb ? ob : nb;
+            owndot += __shfl_xor(owndot, of, 64);
+        }
+        if (lane == 0) {
+            const double* __restrict__ so = stat + EV_STAT * own;
+            const double cn = so[0], n2 = so[1], m2 = so[3], m1 = so[4];
+            double ownd;
+            if (dist == 0) {
+                const double q = m2 + oacc;
+                ownd = sqrt(q > 0.0 ? q : 0.0);
+            } else if (dist == 1) {
+                const double cross = sqrt(xn) * sqrt(m2);
+                ownd = cross > 0.0 ? 1.0 - owndot / cross : 1.0;
+            } else {
+                ownd = m1 + oacc;
+            }
+            ev_store(o, dist, ownd, ev_dis(dist, owndot, xn, cn, n2), nb, cn);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+// The row pass over n fp64 rows X [n, d] (1 <= d <= 1024, 8-byte aligned) with clusters cid int32 [n]: img is the
+// mean image of ``ops/kmeans_dense64._centroid_image`` (COSINE code) for tiles-per-block nt (1, 2, 4 or 8), nblk
+// blocks of 16 nt cluster slots; mean [k, d]; stat [nblk * 16 nt, 8] = the cluster records (cnt, n2,
+// 1 / max(cnt, 1), |m|^2, sum |m|, 0, 0, 0; the dense kernel reads the first three), padded with zeros; dist 0
+// EUCLIDEAN, 1 COSINE, 2 CITYBLOCK.  out [n, 3]: every element is written.
+int alink_evalcluster_rows_f64(const double* X, int64_t n, int d, const int* cid, const double* img,
+                               const double* mean, const double* stat, int k, int nt, int nblk, int dist, double* out,
+                               int grid, void* stream) {
+    if (n <= 0) return 0;
+    if (d < 1 || d > 1024 || k < 1 || nblk < 1 || (int64_t)nblk * nt * 16 < k || n >= (1ll << 31)) return 1;
+    if (nt != 1 && nt != 2 && nt != 4 && nt != 8) return 1;
+    if (dist < 0 || dist > 2) return 1;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int ndch = (d + EV_DCH - 1) / EV_DCH;
+    int64_t blocks = (n + EV_ROWS - 1) / EV_ROWS;
+    const int64_t cap = grid > 0 ? grid : 1024;
+    if (blocks > cap) blocks = cap;
+    const dim3 g((unsigned)blocks), b(64 * EV_WAVES);
+    const bool vec = d % 2 == 0 && reinterpret_cast<uintptr_t>(X) % 16 == 0 &&
+                     reinterpret_cast<uintptr_t>(mean) % 16 == 0;
+#define ALINK_EV_ROWS(NT)                                                                                          \
+    do {                                                                                                           \
+        if (vec)                                                                                                   \
+            hipLaunchKernelGGL((evalcluster_rows_f64_kernel<NT, true>), g, b, 0, st, X, n, d, cid, img, mean,      \
+                               stat, k, nblk, ndch, dist, out);                                                    \
+        else                                                                                                       \
+            hipLaunchKernelGGL((evalcluster_rows_f64_kernel<NT, false>), g, b, 0, st, X, n, d, cid, img, mean,     \
+                               stat, k, nblk, ndch, dist, out);                                                    \
+    } while (0)
+    if (nt == 1) ALINK_EV_ROWS(1);
+    else if (nt == 2) ALINK_EV_ROWS(2);
+    else if (nt == 4) ALINK_EV_ROWS(4);
+    else ALINK_EV_ROWS(8);
+#undef ALINK_EV_ROWS
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// The row pass over n CSR rows (crow int64 [n+1]; col int32, or int64 with idx64; val fp64) under d columns with
+// clusters cid int32 [n]: Mt [d, kp] the transposed means (kp a multiple of 64, k <= kp), stat [kp, 8] the same
+// cluster records, padded with zeros; dist as above.  out [n, 3]: every element is written.
+int alink_evalcluster_rows_csr(const int64_t* crow, const void* col, int idx64, const double* val, int64_t n,
+                               int64_t d, const int* cid, const double* Mt, const double* stat, int k, int kp,
+                               int dist, double* out, int grid, void* stream) {
+    if (n <= 0) return 0;
+    if (d < 1 || k < 1 || kp < 64 || kp % 64 != 0 || k > kp || n >= (1ll << 31)) return 1;
+    if (dist < 0 || dist > 2) return 1;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    int64_t blocks = (n + EV_WAVES - 1) / EV_WAVES;
+    const int64_t cap = grid > 0 ? grid : 16384;
+    if (blocks > cap) blocks = cap;
+    const dim3 g((unsigned)blocks), b(64 * EV_WAVES);
+#define ALINK_EV_CSR(NB, U)                                                                                        \
+    do {                                                                                                           \
+        if (idx64)                                                                                                 \
+            hipLaunchKernelGGL((evalcluster_rows_csr_kernel<NB, U, int64_t>), g, b, 0, st, crow,                   \
+                               reinterpret_cast<const int64_t*>(col), val, n, d, cid, Mt, stat, k, kp, dist, out); \
+        else                                                                                                       \
+            hipLaunchKernelGGL((evalcluster_rows_csr_kernel<NB, U, int32_t>), g, b, 0, st, crow,                   \
+                               reinterpret_cast<const int32_t*>(col), val, n, d, cid, Mt, stat, k, kp, dist, out); \
+    } while (0)
+    if (kp == 64) ALINK_EV_CSR(1, 8);
+    else if (kp == 128) ALINK_EV_CSR(2, 8);
+    else ALINK_EV_CSR(4, 4);
+#undef ALINK_EV_CSR
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+}  // extern "C"

@@ -110,13 +110,16 @@ class Rows:
             return slot
         return self._descend(table, slot, int(levels), grid)
 
-    def child_stats(self, slot: torch.Tensor, nslots: int, sqnorm: bool = True, grid: int = 0) -> torch.Tensor:
+    def child_stats(self, slot: torch.Tensor, nslots: int, sqnorm: bool = True, grid: int = 0,
+                    work=None) -> torch.Tensor:
         """fp64 ``[nslots, d + 2] = [sum_x | count | sum |x|^2]`` of the rows per slot; rows whose slot is outside
         ``[0, nslots)`` add nothing.  ``sqnorm=False`` may leave the last column zero (only the EUCLIDEAN cost reads
-        it).  An empty partition launches nothing."""
+        it).  An empty partition launches nothing.  ``work``: the sorted work list of these slots
+        (``kmeans_dense64._sorted_work(slot, nslots, ignore_outside=True)``) where the caller has it already; the
+        HIP kinds then do not sort again, the torch kinds never sort."""
         if self.n == 0:
             return torch.zeros((int(nslots), self.d + 2), dtype=torch.float64, device=slot.device)
-        return self._child_stats(slot, int(nslots), sqnorm, grid)
+        return self._child_stats(slot, int(nslots), sqnorm, grid, work)
 
     def row_sqnorm(self) -> torch.Tensor:
         """|x|^2 per row, fp64 [n], computed once per rows object."""
@@ -204,7 +207,7 @@ class _SparseRows(Rows):
             return bops.descend_csr(self.X, table, slot, levels, grid)
         return _torch_descend(lambda M: torch.cat([dot for _, dot in self._dot_chunks(M)]), table, slot, levels)
 
-    def _child_stats(self, slot, nslots, sqnorm, grid):
+    def _child_stats(self, slot, nslots, sqnorm, grid, work=None):
         fm, d = self.X, self.d
         buf = torch.zeros((nslots, d + 2), dtype=torch.float64, device=fm.device)
         idx = torch.where((slot >= 0) & (slot < nslots), slot, torch.full_like(slot, -1)).to(torch.int32)
@@ -212,8 +215,9 @@ class _SparseRows(Rows):
         if ksp._use_hip(fm):
             buf[:, :d + 1] = ksp.accumulate_hip(fm, idx.contiguous(), nslots, d, counts, grid)
             if sqnorm:      # the per-row norms through the dense accumulate at d = 1: no float atomics here either
-                buf[:, d + 1] = kd64.accumulate(self.row_sqnorm()[:, None], idx, nslots, grid,
-                                                ignore_outside=True)[:, 0]
+                sq = self.row_sqnorm()[:, None]
+                buf[:, d + 1] = (kd64.accumulate(sq, idx, nslots, grid, ignore_outside=True) if work is None else
+                                 kd64._accumulate_work(sq, work, nslots, grid))[:, 0]
             return buf
         key = torch.where(idx >= 0, idx, torch.full_like(idx, nslots)).to(torch.int64)      # a spare last slot
         buf[:, :d + 1] = ksp._accumulate_torch(fm, key, nslots + 1, d)[:nslots]
@@ -268,7 +272,7 @@ class _TorchRows(Rows):
     def _descend(self, table, slot, levels, grid):
         return _torch_descend(lambda M: self.X @ M.T, table, slot, levels)
 
-    def _child_stats(self, slot, nslots, sqnorm, grid):
+    def _child_stats(self, slot, nslots, sqnorm, grid, work=None):
         # segment sums as one [m, n] x [n, d + 2] GEMM over the rows that have a slot
         from .gemm import tn_matmul
         X, d = self.X, self.d
@@ -321,12 +325,13 @@ class _Dense64Rows(_TorchRows):
             return bops.descend_f64(self.X, table, slot, levels, grid)
         return super()._descend(table, slot, levels, grid)
 
-    def _child_stats(self, slot, nslots, sqnorm, grid):
+    def _child_stats(self, slot, nslots, sqnorm, grid, work=None):
         if not kd64._use_hip(self.X, nslots):
             return super()._child_stats(slot, nslots, sqnorm, grid)
         # one stable sort of the slots serves both accumulates; rows without a slot sort last and are not read
         X, d = self.X, self.d
-        work = kd64._sorted_work(slot, nslots, ignore_outside=True)
+        if work is None:
+            work = kd64._sorted_work(slot, nslots, ignore_outside=True)
         buf = torch.zeros((nslots, d + 2), dtype=torch.float64, device=X.device)
         buf[:, :d + 1] = kd64._accumulate_work(X, work, nslots, grid)
         if sqnorm:
