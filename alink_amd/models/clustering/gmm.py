@@ -13,6 +13,12 @@ MI355X design: one EM step = a batched ``[n, k]`` log-density evaluation (``(X -
 ``W_k = U diag(lambda^-1/2)``), a log-sum-exp, and the weighted moment sums ``R^T X`` and
 ``X^T diag(r_k) X`` as GEMMs — all on the device — followed by ONE all-reduce of the
 ``k (1 + d + d^2) + 1`` statistics buffer (the reference's reduce-to-one + broadcast).
+
+fp64 GPU rows with d <= 128 (``ops/gmm.em_selected``; ``ALINK_GMM_HIP=0`` turns it off) take the fused EM step
+instead: ``ops/gmm.em_step`` is one E pass and one M pass of ``csrc/gmm_em.hip`` with no ``[n, k d]`` buffer, the
+all-reduced statistics are those of the rows centred by the global mean (``mu = xbar + xs / rs``,
+``Sigma = xxs / rs - mu0 mu0^T`` with ``mu0 = xs / rs``, which does not lose precision to a large common offset),
+and ``GmmModelMapper`` predicts through ``ops/gmm.posterior`` with the prediction column built on the device.
 """
 from __future__ import annotations
 
@@ -164,8 +170,28 @@ def train_gmm(mt: MTable, params: Params, env) -> List[tuple]:
     comm.all_reduce(xs_n, "sum")
     xbar = xs_n[:d] / xs_n[d].clamp(min=1.0)
     X0 = X - xbar
+    # the fused EM step (ops/gmm.em_step) where every rank's rows allow it (a rank without rows adds zeros either
+    # way): the statistics are then those of the centred rows
+    flags = comm.all_gather_object((bool(gmm_ops.em_selected(X0, k)), int(X0.shape[0])))
+    fused = any(sel for sel, _ in flags) and all(sel or rows == 0 for sel, rows in flags)
     for step in range(1, max_iter + 1):
         Wr, logdet, rank = _root_inv(S)
+        if fused:
+            rs, xs, xxs, ll, _ = gmm_ops.em_step(X0, mu - xbar, Wr, logdet, rank, torch.log(w))
+            stats = torch.cat([rs, xs.reshape(-1), xxs.reshape(-1), ll.reshape(1),
+                               torch.tensor([float(X0.shape[0])], dtype=X0.dtype, device=dev)])
+            comm.all_reduce(stats, "sum")
+            rs = stats[:k]
+            mu0 = stats[k:k + k * d].reshape(k, d) / rs[:, None]
+            xxs = stats[k + k * d:k + k * d + k * d * d].reshape(k, d, d)
+            ll = float(stats[-2])
+            mu = xbar + mu0
+            S = xxs / rs[:, None, None] - mu0[:, :, None] * mu0[:, None, :]
+            w = rs / float(stats[-1])
+            if step > 1 and abs(ll - prev) <= tol:
+                break
+            prev = ll
+            continue
         R, lse_sum = gmm_ops.estep(X0, mu - xbar, Wr, logdet, rank, torch.log(w))
         stats = torch.cat([R.sum(0), tn_matmul(R, X).reshape(-1),
                            _weighted_syrk(R, X).reshape(-1), lse_sum.reshape(1),
@@ -229,13 +255,28 @@ class GmmModelMapper(RichModelMapper):
             # pseudo-inverse roots once per mapper, on the host (small k x d x d eigh), then kept on X's device
             W, logdet, rank = _root_inv(torch.as_tensor(self.S))
             f = self._factors = tuple(t.to(X.device) for t in (torch.as_tensor(self.mu), W, logdet, rank))
+        if gmm_ops.em_selected(X, self.k):
+            return self._map_columns_posterior(X, f)
         lp = _logpdf_root(X, *f).cpu().numpy()
         lw = lp + np.log(self.w)[None, :]
         m = lw.max(1, keepdims=True)
         prob = np.exp(lw - m)
         prob = prob / prob.sum(1, keepdims=True)
         pred = prob.argmax(1)
-        cols = [Column(torch.from_numpy(pred.astype(np.int64)))]
+        return self._pred_columns(torch.from_numpy(pred.astype(np.int64)), prob)
+
+    def _map_columns_posterior(self, X, f):
+        """The device route (``ops/gmm.posterior``): rows centred by the mixture mean ``sum_j w_j mu_j``, the
+        prediction column built on the device, the responsibilities read back only for a detail column."""
+        mu, W, logdet, rank = f
+        w = torch.as_tensor(self.w, device=X.device)
+        centre = (w[:, None] * mu).sum(0)
+        pred, prob = gmm_ops.posterior(X - centre, mu - centre, W, logdet, rank, torch.log(w),
+                                       bool(self.detail_col))
+        return self._pred_columns(pred, prob.cpu().numpy() if prob is not None else None)
+
+    def _pred_columns(self, pred, prob):
+        cols = [Column(pred)]
         if self.detail_col:
             from ... import _native
             r = _native.java_double_rows_packed(prob, " ") if len(prob) else None
