@@ -5,7 +5,9 @@ product :39-73), per-row bisection for the Gaussian precision ``beta`` matching 
 (``solveForBeta`` :75-108, 100 iterations, tolerance 1e-2 on log-perplexity), binding probabilities
 :133-172, outlier probability = prod_i (1 - b_ij) :174-203; ``SosBatchOp.java``.
 
-MI355X-first: the n x n dissimilarity matrix is ONE GEMM (``|x|^2 + |y|^2 - 2 X X^T``) on the device, the
+Contiguous fp64 GPU rows at most ``ops.sos.SOS_MAX_D`` wide go through ``ops/sos.py`` (``csrc/sos.hip``: the search
+and the column products with D recomputed on the fp64 matrix cores, no [block, n] buffer), unless ``ALINK_SOS_HIP=0``
+or the search ends in a state that is not finite.  Otherwise: the n x n dissimilarity matrix is ONE GEMM (``|x|^2 + |y|^2 - 2 X X^T``) on the device, the
 bisection runs for all rows at once (vectorised state with per-row convergence masks, so every row follows
 exactly the reference's iteration sequence), and the column products are a log-sum reduction — rows are
 processed in blocks so memory stays bounded.
@@ -30,6 +32,11 @@ def _log_h(D: torch.Tensor, beta: torch.Tensor, self_mask: torch.Tensor) -> torc
 
 def sos_scores(X: torch.Tensor, perplexity: float, block: int = 4096) -> torch.Tensor:
     """Outlier probability of every row of X [n, d] (float64)."""
+    from ...ops import sos as K
+    if K.sos_selected(X):       # csrc/sos.hip: the search and the products fused, D never stored
+        out = K.scores(X, perplexity)
+        if out is not None:
+            return out
     n = X.shape[0]
     X = X.to(torch.float64)
     sq = (X * X).sum(1)

@@ -6,6 +6,8 @@ side output 0 = rules), ``A/operator/batch/outlier/SosBatchOp.java``,
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 
@@ -95,6 +97,27 @@ def _dense_block(values, device) -> torch.Tensor:
     return torch.as_tensor(X, device=device)
 
 
+def _sos_device_block(table, col, device):
+    """The vector column as fp64 rows on a GPU device without a pass through Python vectors: a dense block as it
+    is, a CSR block at most ``ops.sos.SOS_DMAX`` wide densified on the device.  None for CPU devices, fp32 blocks,
+    wider sparse columns and ``ALINK_SOS_HIP=0``: those keep ``_dense_block``."""
+    from ...common.linalg import SparseBlock
+    from ...ops import sos as S
+    if torch.device(device).type != "cuda" or os.environ.get("ALINK_SOS_HIP", "") == "0":
+        return None
+    v = table.col(col).values
+    if isinstance(v, SparseBlock):
+        if v.size > S.SOS_DMAX:
+            return None
+    elif isinstance(v, torch.Tensor) and v.dim() == 2:
+        if v.dtype != torch.float64:
+            return None
+    fm = _lsh_columns(table, col, device)
+    if fm.is_sparse and fm.ncols > S.SOS_DMAX:
+        return None
+    return fm.to_dense().contiguous()
+
+
 class SosBatchOp(BatchOperator):
     """Outlier probability per row; the n x n affinity work is split by row blocks across ranks and the
     per-column log-products are all-reduced."""
@@ -103,7 +126,9 @@ class SosBatchOp(BatchOperator):
         mt = self.checkAndGetFirst(inputs).getOutputTable()
         p = self.resolvedParams()
         full = gather_table(mt)
-        X = _dense_block(full.col(p.get("vectorCol")).to_list(), self.env.device)
+        X = _sos_device_block(full, p.get("vectorCol"), self.env.device)
+        if X is None:
+            X = _dense_block(full.col(p.get("vectorCol")).to_list(), self.env.device)
         scores = sos_scores(X, float(p.get("perplexity")))
         lo, hi = (0, full.num_rows) if mt.replicated or comm.get_world_size() == 1 else \
             partition_bounds(full.num_rows, self.env)
