@@ -12,21 +12,20 @@
 //        when there is no other cluster; sil = cur < nb ? 1 - cur / nb : nb / cur - 1, NaN -> 0.
 //   A row whose cid is outside [0, k) gets [0, 0, 0] and no mean is read for it.
 //
-// * alink_evalcluster_rows_f64 — dense fp64 rows [n, d], 1 <= d <= 1024.  The k dots are the problem of
-//   dense64_nearest_kernel (kmeans_dense64.hip) and are solved the same way: a workgroup of 4 waves takes 64 rows
-//   (a wave its 16), walks the clusters in blocks of 16 NT and the dims in chunks of 32, and runs
-//   v_mfma_f64_16x16x4_f64 with the mean tile as A and the rows as B; the mean block of a dim chunk is staged in LDS
-//   from the lane-ordered image of ``kmeans_dense64._centroid_image`` (COSINE code: plain dots, accumulators start at
-//   0).  d is zero-padded in the registers; odd d and 8-byte-aligned rows take scalar loads (VEC = false).
+// * alink_evalcluster_rows_f64 — dense fp64 rows [n, d], 1 <= d <= 1024.  The k dots run on the
+//   tile loop of dense64_mfma.h (the table is the cluster means; operand maps and image layout are described
+//   there): 64 rows per workgroup, blocks of 16 NT clusters, dim chunks of 32, the image of
+//   ``kmeans_dense64.centroid_image`` with the COSINE code (plain dots, accumulators start at 0).  d is zero-padded
+//   in the registers; odd d and 8-byte-aligned rows take scalar loads (VEC = false).
 //   The epilogue walks the lane's own 4 NT accumulators (clusters g + 4 q of each tile), then the four lane groups:
 //   a min that skips j == cid and every j >= k, and the own-cluster dot picked out by index.  |x|^2 is summed per
 //   lane in ascending dim order and combined by a fixed xor butterfly (16, 32) before the epilogue.
 //   own comes from the row's registers against a gather of mean[cid] (32 contiguous bytes per lane and 16-dim
 //   group, served by L2: the table is k d doubles), each lane adding in ascending dim order, the same butterfly
 //   across the lane groups: the three outputs depend on the row alone, not on the grid or the row's wave.
-//   Choices: LDS 4 NT KiB per workgroup (<= 32 KiB, so LDS never limits below 5 workgroups per CU); the image is
-//   written in lane order, 32 bytes per lane, so the ds_read_b128 pairs are conflict-free; 256-thread workgroups
-//   so that one staged block serves 64 rows; the grid is capped at 1024 workgroups that stride over the row batches.
+//   Choices: LDS 4 NT KiB per workgroup (<= 32 KiB, so LDS never limits below 5 workgroups per CU); 256-thread
+//   workgroups so that one staged block serves 64 rows; the grid is capped at 1024 workgroups that stride over the
+//   row batches.
 // * alink_evalcluster_rows_csr — CSR rows (int32 / int64 columns), one wave per row, as sparse_nearest_kernel
 //   (kmeans_sparse.hip): the means come transposed and padded, Mt [d, kp], lane l owns clusters l, l + 64, ... of a
 //   block of up to 256 clusters, 64 entries are loaded at a time and walked in stored order with wave-uniform
@@ -44,32 +43,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dense64_mfma.h"
+#include "lane_bcast.h"
+
 namespace {
 
-typedef double d4_t __attribute__((ext_vector_type(4)));
-typedef double d2_t __attribute__((ext_vector_type(2)));
+using namespace d64;
+using lane::bcast_f64;
+using lane::bcast_i64;
 
-constexpr int EV_WAVES = 4;          // waves per workgroup
-constexpr int EV_ROWS = 16 * EV_WAVES;
-constexpr int EV_DCH = 32;           // dims per staged chunk (two 16-dim groups u = 0, 1)
+constexpr int EV_CSR_WAVES = 4;      // waves (rows) per workgroup of the CSR kernel
 constexpr int EV_NB = 4;             // cluster blocks of 64 a lane of the CSR kernel holds at most
 constexpr int EV_STAT = 8;           // doubles per cluster record: cnt, n2, 1 / max(cnt, 1), |m|^2, sum |m|, padding
-
-__device__ __forceinline__ d4_t mf64(double a, double b, d4_t c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ double bcast_f64(double v, int lane) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ int64_t bcast_i64(int64_t v, int lane) {
-    const int lo = __builtin_amdgcn_readlane((int)(v & 0xffffffffll), lane);
-    const int hi = __builtin_amdgcn_readlane((int)(v >> 32), lane);
-    return ((int64_t)hi << 32) | (uint32_t)lo;
-}
 
 // dis_j of the closed form from the dot x.m_j
 __device__ __forceinline__ double ev_dis(int dist, double dot, double xn, double cn, double n2) {
@@ -88,22 +73,20 @@ __device__ __forceinline__ void ev_store(double* __restrict__ o, int dist, doubl
     o[2] = sil;
 }
 
-// img: per (cluster block, dim chunk) NT * 512 doubles in [u][tile][g][m][step] order; mean [k, d];
-// stat [nblk * 16 NT, 8] = (cnt, n2, 1 / max(cnt, 1), ...), zero on the padded slots.
-// VEC: d is even and X and mean are 16-byte aligned, so a lane's four dims are two aligned 16-byte loads.
+// img: the mean image (dense64_mfma.h); mean [k, d]; stat [nblk * 16 NT, 8] = (cnt, n2, 1 / max(cnt, 1), ...), zero
+// on the padded slots.  VEC: even d and 16-byte aligned X and mean (load_chunk).
 template <int NT, bool VEC>
-__global__ __launch_bounds__(64 * EV_WAVES) void evalcluster_rows_f64_kernel(
+__global__ __launch_bounds__(64 * WAVES) void evalcluster_rows_f64_kernel(
         const double* __restrict__ X, int64_t n, int d, const int* __restrict__ cid, const double* __restrict__ img,
         const double* __restrict__ mean, const double* __restrict__ stat, int k, int nblk, int ndch, int dist,
         double* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) double cent[NT * 512];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
     const int m = lane & 15, g = lane >> 4;
-    const int64_t nbatch = (n + EV_ROWS - 1) / EV_ROWS;
+    const int64_t nbatch = (n + ROWS - 1) / ROWS;
     for (int64_t b = blockIdx.x; b < nbatch; b += gridDim.x) {
-        const int64_t row = b * EV_ROWS + wave * 16 + m;
+        const int64_t row = b * ROWS + wave * 16 + m;
         const bool row_ok = row < n;
         const double* __restrict__ xr = X + (row_ok ? row : 0) * (int64_t)d;
         const int own = row_ok ? cid[row] : -1;
@@ -119,43 +102,13 @@ __global__ __launch_bounds__(64 * EV_WAVES) void evalcluster_rows_f64_kernel(
             for (int t = 0; t < NT; ++t) acc[t] = d4_t{0.0, 0.0, 0.0, 0.0};
             xn = 0.0;
             for (int dc = 0; dc < ndch; ++dc) {
-                // this lane's dims of the row: dc * 32 + 16 u + 4 g + s; outside the row they are zero
+                // this lane's dims of the row (zero outside it)
                 double xb[2][4];
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const int j0 = dc * EV_DCH + 16 * u + 4 * g;
-                    if (VEC) {
-#pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            d2_t v = {0.0, 0.0};
-                            if (row_ok && j0 + 2 * h < d) v = *reinterpret_cast<const d2_t*>(xr + j0 + 2 * h);
-                            xb[u][2 * h] = v[0];
-                            xb[u][2 * h + 1] = v[1];
-                        }
-                    } else {
-#pragma unroll
-                        for (int s = 0; s < 4; ++s) xb[u][s] = (row_ok && j0 + s < d) ? xr[j0 + s] : 0.0;
-                    }
-                }
+                load_chunk<VEC>(xb, xr, row_ok, dc, g, d);
                 if (cb == 0) {
                     // the same dims of the row's own mean; the sums run in ascending dim order within the lane
                     double mb[2][4];
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) {
-                        const int j0 = dc * EV_DCH + 16 * u + 4 * g;
-                        if (VEC) {
-#pragma unroll
-                            for (int h = 0; h < 2; ++h) {
-                                d2_t v = {0.0, 0.0};
-                                if (own_ok && j0 + 2 * h < d) v = *reinterpret_cast<const d2_t*>(mr + j0 + 2 * h);
-                                mb[u][2 * h] = v[0];
-                                mb[u][2 * h + 1] = v[1];
-                            }
-                        } else {
-#pragma unroll
-                            for (int s = 0; s < 4; ++s) mb[u][s] = (own_ok && j0 + s < d) ? mr[j0 + s] : 0.0;
-                        }
-                    }
+                    load_chunk<VEC>(mb, mr, own_ok, dc, g, d);
 #pragma unroll
                     for (int u = 0; u < 2; ++u) {
 #pragma unroll
@@ -173,36 +126,16 @@ __global__ __launch_bounds__(64 * EV_WAVES) void evalcluster_rows_f64_kernel(
                         }
                     }
                 }
-                // stage the mean block of this dim chunk: a straight copy of NT * 4 KiB
-                const d2_t* __restrict__ src =
-                    reinterpret_cast<const d2_t*>(img + ((int64_t)cb * ndch + dc) * (NT * 512));
-                __syncthreads();        // the previous chunk's reads are done
-#pragma unroll
-                for (int i = 0; i < NT; ++i)
-                    reinterpret_cast<d2_t*>(cent)[i * 256 + tid] = src[i * 256 + tid];
-                __syncthreads();
+                stage<NT>(cent, img, cb, ndch, dc);     // the mean block of this dim chunk
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
 #pragma unroll
                     for (int s = 0; s < 4; ++s) xn = fma(xb[u][s], xb[u][s], xn);
-#pragma unroll
-                    for (int t0 = 0; t0 < NT; t0 += 4) {
-                        d4_t a[NT < 4 ? NT : 4];
-#pragma unroll
-                        for (int t = 0; t < (NT < 4 ? NT : 4); ++t)
-                            a[t] = *reinterpret_cast<const d4_t*>(cent + (((u * NT + t0 + t) * 4 + g) * 16 + m) * 4);
-#pragma unroll
-                        for (int s = 0; s < 4; ++s) {
-#pragma unroll
-                            for (int t = 0; t < (NT < 4 ? NT : 4); ++t)
-                                acc[t0 + t] = mf64(a[t][s], xb[u][s], acc[t0 + t]);
-                        }
-                    }
+                    mfma_group<NT>(acc, cent, xb[u], u, g, m);
                 }
             }
-            // |x|^2 of the whole row on every lane group: both partners add the same two values
-#pragma unroll
-            for (int o = 16; o < 64; o <<= 1) xn += __shfl_xor(xn, o, 64);
+            // |x|^2 of the whole row on every lane group
+            xn = group_sum(xn);
             // the lane's own clusters: tile, then register
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
@@ -226,10 +159,10 @@ __global__ __launch_bounds__(64 * EV_WAVES) void evalcluster_rows_f64_kernel(
         for (int o = 16; o < 64; o <<= 1) {
             const double ob = __shfl_xor(nb, o, 64);
             nb = ob < nb ? ob : nb;
-            owndot += __shfl_xor(owndot, o, 64);
-            a0 += __shfl_xor(a0, o, 64);
-            a1 += __shfl_xor(a1, o, 64);
         }
+        owndot = group_sum(owndot);
+        a0 = group_sum(a0);
+        a1 = group_sum(a1);
         if (g == 0 && row_ok) {
             double* __restrict__ o = out + row * 3;
             if (!own_ok) {
@@ -257,13 +190,13 @@ __global__ __launch_bounds__(64 * EV_WAVES) void evalcluster_rows_f64_kernel(
 // NB: cluster blocks of 64 per pass (kp >= 64 * NB unless NB == EV_NB, where the tail block is guarded);
 // U: entries whose gathers are issued together.
 template <int NB, int U, typename I>
-__global__ __launch_bounds__(64 * EV_WAVES) void evalcluster_rows_csr_kernel(
+__global__ __launch_bounds__(64 * EV_CSR_WAVES) void evalcluster_rows_csr_kernel(
         const int64_t* __restrict__ crow, const I* __restrict__ col, const double* __restrict__ val, int64_t n,
         int64_t d, const int* __restrict__ cid, const double* __restrict__ Mt, const double* __restrict__ stat, int k,
         int kp, int dist, double* __restrict__ out) {
     const int lane = threadIdx.x & 63;
-    const int64_t w0 = (int64_t)blockIdx.x * EV_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t nw = (int64_t)gridDim.x * EV_WAVES;
+    const int64_t w0 = (int64_t)blockIdx.x * EV_CSR_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nw = (int64_t)gridDim.x * EV_CSR_WAVES;
     for (int64_t r = w0; r < n; r += nw) {
         const int64_t s = crow[r], e = crow[r + 1];
         const int own = __builtin_amdgcn_readfirstlane(cid[r]);
@@ -374,7 +307,7 @@ __global__ __launch_bounds__(64 * EV_WAVES) void evalcluster_rows_csr_kernel(
 extern "C" {
 
 // The row pass over n fp64 rows X [n, d] (1 <= d <= 1024, 8-byte aligned) with clusters cid int32 [n]: img is the
-// mean image of ``ops/kmeans_dense64._centroid_image`` (COSINE code) for tiles-per-block nt (1, 2, 4 or 8), nblk
+// mean image of ``ops/kmeans_dense64.centroid_image`` (COSINE code) for tiles-per-block nt (1, 2, 4 or 8), nblk
 // blocks of 16 nt cluster slots; mean [k, d]; stat [nblk * 16 nt, 8] = the cluster records (cnt, n2,
 // 1 / max(cnt, 1), |m|^2, sum |m|, 0, 0, 0; the dense kernel reads the first three), padded with zeros; dist 0
 // EUCLIDEAN, 1 COSINE, 2 CITYBLOCK.  out [n, 3]: every element is written.
@@ -383,30 +316,13 @@ int alink_evalcluster_rows_f64(const double* X, int64_t n, int d, const int* cid
                                int grid, void* stream) {
     if (n <= 0) return 0;
     if (d < 1 || d > 1024 || k < 1 || nblk < 1 || (int64_t)nblk * nt * 16 < k || n >= (1ll << 31)) return 1;
-    if (nt != 1 && nt != 2 && nt != 4 && nt != 8) return 1;
+    if (!nt_ok(nt)) return 1;
     if (dist < 0 || dist > 2) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int ndch = (d + EV_DCH - 1) / EV_DCH;
-    int64_t blocks = (n + EV_ROWS - 1) / EV_ROWS;
-    const int64_t cap = grid > 0 ? grid : 1024;
-    if (blocks > cap) blocks = cap;
-    const dim3 g((unsigned)blocks), b(64 * EV_WAVES);
-    const bool vec = d % 2 == 0 && reinterpret_cast<uintptr_t>(X) % 16 == 0 &&
-                     reinterpret_cast<uintptr_t>(mean) % 16 == 0;
-#define ALINK_EV_ROWS(NT)                                                                                          \
-    do {                                                                                                           \
-        if (vec)                                                                                                   \
-            hipLaunchKernelGGL((evalcluster_rows_f64_kernel<NT, true>), g, b, 0, st, X, n, d, cid, img, mean,      \
-                               stat, k, nblk, ndch, dist, out);                                                    \
-        else                                                                                                       \
-            hipLaunchKernelGGL((evalcluster_rows_f64_kernel<NT, false>), g, b, 0, st, X, n, d, cid, img, mean,     \
-                               stat, k, nblk, ndch, dist, out);                                                    \
-    } while (0)
-    if (nt == 1) ALINK_EV_ROWS(1);
-    else if (nt == 2) ALINK_EV_ROWS(2);
-    else if (nt == 4) ALINK_EV_ROWS(4);
-    else ALINK_EV_ROWS(8);
-#undef ALINK_EV_ROWS
+    const int ndch = (d + DCH - 1) / DCH;
+    const bool vec = vec_ok(d, X) && vec_ok(d, mean);
+    ALINK_D64_LAUNCH(evalcluster_rows_f64_kernel, nt, 1, 2, 4, 8, vec, row_blocks(n, grid, 1024), st, X, n, d, cid,
+                     img, mean, stat, k, nblk, ndch, dist, out);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -420,10 +336,10 @@ int alink_evalcluster_rows_csr(const int64_t* crow, const void* col, int idx64, 
     if (d < 1 || k < 1 || kp < 64 || kp % 64 != 0 || k > kp || n >= (1ll << 31)) return 1;
     if (dist < 0 || dist > 2) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    int64_t blocks = (n + EV_WAVES - 1) / EV_WAVES;
+    int64_t blocks = (n + EV_CSR_WAVES - 1) / EV_CSR_WAVES;
     const int64_t cap = grid > 0 ? grid : 16384;
     if (blocks > cap) blocks = cap;
-    const dim3 g((unsigned)blocks), b(64 * EV_WAVES);
+    const dim3 g((unsigned)blocks), b(64 * EV_CSR_WAVES);
 #define ALINK_EV_CSR(NB, U)                                                                                        \
     do {                                                                                                           \
         if (idx64)                                                                                                 \

@@ -2,13 +2,13 @@
 // 1 <= d <= 128, any k >= 1, n < 2^31, all arithmetic fp64.  No [n, k d] buffer anywhere.
 //
 // * alink_gmm_em_rows_f64 — the E pass.  Every projection z_j = X0 W_j - C_j (C_j = (mu_j - xbar) W_j) on
-//   v_mfma_f64_16x16x4_f64 with the loop of the dense nearest kernel (kmeans_dense64.hip): the columns of all W_j
-//   are the "centroids", [k dpad, d] with dpad = d rounded up to 16, so a tile of 16 columns never straddles two
-//   components; padded columns are zero in W and in C and add nothing.  A workgroup of 4 waves takes 64 rows at a
-//   time (a wave its 16) and keeps their dims in registers for the whole walk over the components.  The MFMA's A
-//   operand is the column tile (row = column lane & 15, k = lane >> 4), its B operand the data rows, so the result
-//   holds one data row per lane column (lane & 15) and the four columns (lane >> 4) + 4 q of the tile per lane
-//   (the f64 C/D map).  The image is staged in LDS in groups of GT tiles x all dim chunks (32 KiB at most): at
+//   v_mfma_f64_16x16x4_f64 with the operand maps, the row-chunk load and the butterfly of dense64_mfma.h: the
+//   columns of all W_j are the table, [k dpad, d] with dpad = d rounded up to 16, so a tile of 16 columns never
+//   straddles two components; padded columns are zero in W and in C and add nothing.  A workgroup of 4 waves takes
+//   64 rows at a time (a wave its 16) and keeps their dims in registers for the whole walk over the components; a
+//   lane holds the four columns (lane >> 4) + 4 q of a tile for its own row.  The LDS layout is this kernel's own
+//   (tile outermost; see the layout note of dense64_mfma.h), and so are its staging and its MFMA loop.
+//   The image is staged in LDS in groups of GT tiles x all dim chunks (32 KiB at most): at
 //   d = 128 a component's W_j (128 KiB) does not fit and is streamed in column blocks; |z|^2 separates over the
 //   columns, so streaming is exact; an image of a single group is staged once per workgroup.  Accumulators start
 //   at -C.
@@ -37,69 +37,41 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "dense64_mfma.h"
+
 namespace {
 
-typedef double d4_t __attribute__((ext_vector_type(4)));
-typedef double d2_t __attribute__((ext_vector_type(2)));
+using namespace d64;
 
-constexpr int EM_WAVES = 4;
-constexpr int EM_ROWS = 16 * EM_WAVES;
+constexpr int EM_M_WAVES = 4;        // waves per workgroup of the M pass, one unit each
 constexpr int EM_RED = 1024;         // threads of the log-likelihood reduction
-
-__device__ __forceinline__ d4_t mf64(double a, double b, d4_t c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
-// the four lanes (lane & 15 fixed) that share a data row: both partners add the same two values at each step
-__device__ __forceinline__ double group_sum(double v) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
 
 constexpr int em_group_tiles(int ndch) { return ndch == 1 ? 8 : (ndch == 2 ? 4 : 2); }
 
 // img: per tile and dim chunk 512 doubles in [u][g][m][step] order ([tile][dch] outside), ninit [ngroup * GT * 16].
-// VEC: d is even and X is 16-byte aligned, so a lane's four dims are two aligned 16-byte loads.
+// VEC: even d and 16-byte aligned X (load_chunk).
 template <int NDCH, bool VEC>
-__global__ __launch_bounds__(64 * EM_WAVES) void gmm_em_rows_kernel(
+__global__ __launch_bounds__(64 * WAVES) void gmm_em_rows_kernel(
         const double* __restrict__ X, int64_t n, int d, const double* __restrict__ img,
         const double* __restrict__ ninit, const double* __restrict__ cst, int k, int tpc, int ngroup,
         double* R, int* __restrict__ arg_out, double* __restrict__ part) {
     constexpr int GT = em_group_tiles(NDCH);
     constexpr int TI = GT < 4 ? GT : 4;         // tiles interleaved in the MFMA stream
     __shared__ __attribute__((aligned(16))) double cent[GT * NDCH * 512];
-    __shared__ double wsum[2][EM_WAVES];        // by batch parity: see the end of the batch loop
+    __shared__ double wsum[2][WAVES];        // by batch parity: see the end of the batch loop
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int m = lane & 15, g = lane >> 4;
-    const int64_t nbatch = (n + EM_ROWS - 1) / EM_ROWS;
+    const int64_t nbatch = (n + ROWS - 1) / ROWS;
     for (int64_t b = blockIdx.x; b < nbatch; b += gridDim.x) {
-        const int64_t row = b * EM_ROWS + wave * 16 + m;
+        const int64_t row = b * ROWS + wave * 16 + m;
         const bool row_ok = row < n;
         const double* __restrict__ xr = X + (row_ok ? row : 0) * (int64_t)d;
         // this lane's dims of its row: dc * 32 + 16 u + 4 g + s; outside the row they are zero
         double xb[NDCH][2][4];
 #pragma unroll
-        for (int dc = 0; dc < NDCH; ++dc) {
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int j0 = dc * 32 + 16 * u + 4 * g;
-                if (VEC) {
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        d2_t v = {0.0, 0.0};
-                        if (row_ok && j0 + 2 * h < d) v = *reinterpret_cast<const d2_t*>(xr + j0 + 2 * h);
-                        xb[dc][u][2 * h] = v[0];
-                        xb[dc][u][2 * h + 1] = v[1];
-                    }
-                } else {
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) xb[dc][u][s] = (row_ok && j0 + s < d) ? xr[j0 + s] : 0.0;
-                }
-            }
-        }
+        for (int dc = 0; dc < NDCH; ++dc) load_chunk<VEC>(xb[dc], xr, row_ok, dc, g, d);
         double* __restrict__ rrow = R != nullptr ? R + (row_ok ? row : 0) * (int64_t)k : nullptr;
         double best = -__builtin_inf();
         int besti = 0;
@@ -313,7 +285,7 @@ constexpr int em_group_components(int maxtb) { return maxtb <= 2 ? 4 : 2; }
 
 // MAXTB = min(ceil(d / 16), EM_TB): a narrow d compiles (and pays the registers of) its own tile counts only
 template <int MAXTB>
-__global__ __launch_bounds__(64 * EM_WAVES) void gmm_em_moments_kernel(
+__global__ __launch_bounds__(64 * EM_M_WAVES) void gmm_em_moments_kernel(
         const double* __restrict__ X, const double* __restrict__ R, int64_t n, int d, int k, int64_t chunk_rows,
         int64_t nchunk, double* __restrict__ part) {
     constexpr int JB = em_group_components(MAXTB);
@@ -322,8 +294,8 @@ __global__ __launch_bounds__(64 * EM_WAVES) void gmm_em_moments_kernel(
     const int ng = (k + JB - 1) / JB;
     const int64_t S = (int64_t)d * d + d + 1;
     const int64_t units = nchunk * ng * upg;
-    const int64_t w0 = (int64_t)blockIdx.x * EM_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t nw = (int64_t)gridDim.x * EM_WAVES;
+    const int64_t w0 = (int64_t)blockIdx.x * EM_M_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nw = (int64_t)gridDim.x * EM_M_WAVES;
     for (int64_t un = w0; un < units; un += nw) {
         const int64_t c = un / ((int64_t)ng * upg);
         const int rem = (int)(un - c * (int64_t)ng * upg);
@@ -394,26 +366,9 @@ int alink_gmm_em_rows_f64(const double* X, int64_t n, int d, const double* img, 
     if (ngroup < 1 || (int64_t)ngroup * em_group_tiles(ndch) < (int64_t)k * tpc) return 1;
     if (R != nullptr && (part == nullptr || ll == nullptr)) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int64_t nbatch = (n + EM_ROWS - 1) / EM_ROWS;
-    int64_t blocks = nbatch;
-    const int64_t cap = grid > 0 ? grid : 2048;
-    if (blocks > cap) blocks = cap;
-    const dim3 g((unsigned)blocks), b(64 * EM_WAVES);
-    const bool vec = d % 2 == 0 && reinterpret_cast<uintptr_t>(X) % 16 == 0;
-#define ALINK_EM_ROWS(NDCH)                                                                                        \
-    do {                                                                                                           \
-        if (vec)                                                                                                   \
-            hipLaunchKernelGGL((gmm_em_rows_kernel<NDCH, true>), g, b, 0, st, X, n, d, img, ninit, cst, k, tpc,    \
-                               ngroup, R, arg, part);                                                              \
-        else                                                                                                       \
-            hipLaunchKernelGGL((gmm_em_rows_kernel<NDCH, false>), g, b, 0, st, X, n, d, img, ninit, cst, k, tpc,   \
-                               ngroup, R, arg, part);                                                              \
-    } while (0)
-    if (ndch == 1) ALINK_EM_ROWS(1);
-    else if (ndch == 2) ALINK_EM_ROWS(2);
-    else if (ndch == 3) ALINK_EM_ROWS(3);
-    else ALINK_EM_ROWS(4);
-#undef ALINK_EM_ROWS
+    const int64_t nbatch = (n + ROWS - 1) / ROWS;
+    ALINK_D64_LAUNCH(gmm_em_rows_kernel, ndch, 1, 2, 3, 4, vec_ok(d, X), row_blocks(n, grid, 2048), st, X, n, d, img,
+                     ninit, cst, k, tpc, ngroup, R, arg, part);
     if (R != nullptr) hipLaunchKernelGGL(gmm_em_ll_kernel, dim3(1), dim3(EM_RED), 0, st, part, nbatch, ll);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
@@ -430,11 +385,11 @@ int alink_gmm_em_moments_f64(const double* X, const double* R, int64_t n, int d,
     const int64_t cap = grid > 0 ? grid : 16384;
     const int maxtb = dt < EM_TB ? dt : EM_TB;
     const int64_t groups = (k + em_group_components(maxtb) - 1) / em_group_components(maxtb);
-    int64_t blocks = (nchunk * groups * em_units_per_group(dt) + EM_WAVES - 1) / EM_WAVES;
+    int64_t blocks = (nchunk * groups * em_units_per_group(dt) + EM_M_WAVES - 1) / EM_M_WAVES;
     if (blocks > cap) blocks = cap;
 #define ALINK_EM_MOMENTS(MAXTB)                                                                                    \
-    hipLaunchKernelGGL(gmm_em_moments_kernel<MAXTB>, dim3((unsigned)blocks), dim3(64 * EM_WAVES), 0, st, X, R, n, \
-                       d, k, chunk_rows, nchunk, part)
+    hipLaunchKernelGGL(gmm_em_moments_kernel<MAXTB>, dim3((unsigned)blocks), dim3(64 * EM_M_WAVES), 0, st, X, R,   \
+                       n, d, k, chunk_rows, nchunk, part)
     if (dt == 1) ALINK_EM_MOMENTS(1);
     else if (dt == 2) ALINK_EM_MOMENTS(2);
     else if (dt == 3) ALINK_EM_MOMENTS(3);

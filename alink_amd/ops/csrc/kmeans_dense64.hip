@@ -2,14 +2,10 @@
 // all arithmetic fp64.
 //
 // * alink_kmeans_dense64_nearest — score s[r, c] = x_r . c_c - |c_c|^2 / 2 on v_mfma_f64_16x16x4_f64, argmax per row.
-//   A workgroup of 4 waves takes 64 rows at a time (a wave its 16), and walks the centroids in blocks of 16 NT
-//   (NT = 1, 2, 4 or 8 tiles) and the dims in chunks of 32.  The MFMA's A operand is the centroid tile (row = centroid
-//   lane & 15, k = lane >> 4), its B operand the rows (k = lane >> 4, column = row lane & 15), so the result holds one
-//   data row per lane column and four centroids (lane >> 4) + 4 q per lane: the argmax runs down the lane's own
-//   registers first and across the four lane groups last.  The k order inside a 16-dim group is permuted the same way
-//   on both operands (lane group g owns dims 4 g .. 4 g + 3, one per MFMA step), so a lane's loads of X are 32
-//   contiguous bytes.  The centroid block of a dim chunk is staged in LDS from an image the wrapper laid out in
-//   exactly the order the lanes read it ([u][tile][g][m][step], 32 bytes per lane, conflict-free ds_read_b128).
+//   The tile loop, the operand maps and the lane-ordered centroid image are those of dense64_mfma.h (the table is
+//   the centroids): 64 rows per workgroup, blocks of 16 NT centroids, dim chunks of 32.  A lane holds four centroids
+//   (lane >> 4) + 4 q per tile for its own row: the argmax runs down the lane's own registers first and across the
+//   four lane groups last.
 //   Accumulators start at -|c|^2 / 2 (0 for COSINE).  d is padded to the chunk with zeros in the registers: a load
 //   is issued only for a (row, dim) inside [0, n) x [0, d).  Centroid slots at or past k are skipped by index in the
 //   argmax, so they cannot win whatever the real scores are.  The scan is in ascending centroid index with a
@@ -27,24 +23,19 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dense64_mfma.h"
+#include "lane_bcast.h"
+
 namespace {
 
-typedef double d4_t __attribute__((ext_vector_type(4)));
-typedef double d2_t __attribute__((ext_vector_type(2)));
+using namespace d64;
+using lane::bcast_i64;
 
-constexpr int DN_WAVES = 4;          // waves per workgroup; a wave owns 16 rows of the workgroup's 64
-constexpr int DN_ROWS = 16 * DN_WAVES;
-constexpr int DN_DCH = 32;           // dims per staged chunk (two 16-dim groups u = 0, 1)
 constexpr int DN_HIST = 2048;        // largest k whose counts go through the LDS histogram
 
-__device__ __forceinline__ d4_t mf64(double a, double b, d4_t c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
-// img: per (centroid block, dim chunk) NT * 512 doubles in [u][tile][g][m][step] order; ninit [nblk * 16 NT].
-// VEC: d is even and X is 16-byte aligned, so a lane's four dims are two aligned 16-byte loads.
+// img: the centroid image (dense64_mfma.h); ninit [nblk * 16 NT].  VEC: even d and 16-byte aligned X (load_chunk).
 template <int NT, bool VEC>
-__global__ __launch_bounds__(64 * DN_WAVES) void dense64_nearest_kernel(
+__global__ __launch_bounds__(64 * WAVES) void dense64_nearest_kernel(
         const double* __restrict__ X, int64_t n, int d, const double* __restrict__ img,
         const double* __restrict__ ninit, int k, int nblk, int ndch, int cosine, int* __restrict__ idx_out,
         double* __restrict__ dist_out, unsigned long long* __restrict__ counts) {
@@ -56,12 +47,12 @@ __global__ __launch_bounds__(64 * DN_WAVES) void dense64_nearest_kernel(
     const int m = lane & 15, g = lane >> 4;
     const bool use_hist = counts != nullptr && k <= DN_HIST;
     if (use_hist) {
-        for (int i = tid; i < k; i += 64 * DN_WAVES) hist[i] = 0u;
+        for (int i = tid; i < k; i += 64 * WAVES) hist[i] = 0u;
         // the first barrier of the staging loop orders these stores before any histogram add
     }
-    const int64_t nbatch = (n + DN_ROWS - 1) / DN_ROWS;
+    const int64_t nbatch = (n + ROWS - 1) / ROWS;
     for (int64_t b = blockIdx.x; b < nbatch; b += gridDim.x) {
-        const int64_t row = b * DN_ROWS + wave * 16 + m;
+        const int64_t row = b * ROWS + wave * 16 + m;
         const bool row_ok = row < n;
         const double* __restrict__ xr = X + (row_ok ? row : 0) * (int64_t)d;
         double best = -__builtin_inf();
@@ -76,49 +67,15 @@ __global__ __launch_bounds__(64 * DN_WAVES) void dense64_nearest_kernel(
             }
             xn = 0.0;
             for (int dc = 0; dc < ndch; ++dc) {
-                // this lane's rows of X: dims dc * 32 + 16 u + 4 g + s; outside the row they are zero
+                // this lane's dims of the row (zero outside it), then the centroid block of this dim chunk
                 double xb[2][4];
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const int j0 = dc * DN_DCH + 16 * u + 4 * g;
-                    if (VEC) {
-#pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            d2_t v = {0.0, 0.0};
-                            if (row_ok && j0 + 2 * h < d) v = *reinterpret_cast<const d2_t*>(xr + j0 + 2 * h);
-                            xb[u][2 * h] = v[0];
-                            xb[u][2 * h + 1] = v[1];
-                        }
-                    } else {
-#pragma unroll
-                        for (int s = 0; s < 4; ++s) xb[u][s] = (row_ok && j0 + s < d) ? xr[j0 + s] : 0.0;
-                    }
-                }
-                // stage the centroid block of this dim chunk: a straight copy of NT * 4 KiB
-                const d2_t* __restrict__ src =
-                    reinterpret_cast<const d2_t*>(img + ((int64_t)cb * ndch + dc) * (NT * 512));
-                __syncthreads();        // the previous chunk's reads are done
-#pragma unroll
-                for (int i = 0; i < NT; ++i)
-                    reinterpret_cast<d2_t*>(cent)[i * 256 + tid] = src[i * 256 + tid];
-                __syncthreads();
+                load_chunk<VEC>(xb, xr, row_ok, dc, g, d);
+                stage<NT>(cent, img, cb, ndch, dc);
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
 #pragma unroll
                     for (int s = 0; s < 4; ++s) xn = fma(xb[u][s], xb[u][s], xn);
-#pragma unroll
-                    for (int t0 = 0; t0 < NT; t0 += 4) {
-                        d4_t a[NT < 4 ? NT : 4];
-#pragma unroll
-                        for (int t = 0; t < (NT < 4 ? NT : 4); ++t)
-                            a[t] = *reinterpret_cast<const d4_t*>(cent + (((u * NT + t0 + t) * 4 + g) * 16 + m) * 4);
-#pragma unroll
-                        for (int s = 0; s < 4; ++s) {
-#pragma unroll
-                            for (int t = 0; t < (NT < 4 ? NT : 4); ++t)
-                                acc[t0 + t] = mf64(a[t][s], xb[u][s], acc[t0 + t]);
-                        }
-                    }
+                    mfma_group<NT>(acc, cent, xb[u], u, g, m);
                 }
             }
             // ascending centroid index within the lane: tile, then register
@@ -162,7 +119,7 @@ __global__ __launch_bounds__(64 * DN_WAVES) void dense64_nearest_kernel(
     }
     if (use_hist) {
         __syncthreads();
-        for (int i = tid; i < k; i += 64 * DN_WAVES) {
+        for (int i = tid; i < k; i += 64 * WAVES) {
             const unsigned int h = hist[i];
             if (h != 0u) atomicAdd(counts + i, (unsigned long long)h);
         }
@@ -198,9 +155,7 @@ __global__ __launch_bounds__(64 * AC_WAVES) void dense64_accum_kernel(
                 for (int u = 0; u < AC_U; ++u) {
                     const int q = q0 + u;
                     // q is wave-uniform; lanes past the chunk hold row 0 and are not loaded
-                    const int lo = __builtin_amdgcn_readlane((int)(mine & 0xffffffffll), q & 63);
-                    const int hi = __builtin_amdgcn_readlane((int)(mine >> 32), q & 63);
-                    const int64_t r = ((int64_t)hi << 32) | (uint32_t)lo;
+                    const int64_t r = bcast_i64(mine, q & 63);
                     v[u] = (q < cnt && j_ok) ? X[r * (int64_t)d + j] : 0.0;
                 }
 #pragma unroll
@@ -240,36 +195,19 @@ __global__ __launch_bounds__(256) void dense64_merge_kernel(
 extern "C" {
 
 // Nearest centroid of the n fp64 rows X [n, d] (1 <= d <= 1024).  img / ninit: the centroid image of
-// ``ops/kmeans_dense64._centroid_image`` for tiles-per-block nt (1, 2, 4 or 8): nblk blocks of 16 nt centroid
+// ``ops/kmeans_dense64.centroid_image`` for tiles-per-block nt (1, 2, 4 or 8): nblk blocks of 16 nt centroid
 // slots, ndch = ceil(d / 32) dim chunks.  idx / dist / counts may each be null; counts [k] int64 is added to.
 int alink_kmeans_dense64_nearest(const double* X, int64_t n, int d, const double* img, const double* ninit, int k,
                                  int nt, int nblk, int cosine, int* idx, double* dist, void* counts, int grid,
                                  void* stream) {
     if (n <= 0) return 0;
     if (d < 1 || d > 1024 || k < 1 || nblk < 1 || (int64_t)nblk * nt * 16 < k || n >= (1ll << 31)) return 1;
-    if (nt != 1 && nt != 2 && nt != 4 && nt != 8) return 1;
+    if (!nt_ok(nt)) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int ndch = (d + DN_DCH - 1) / DN_DCH;
-    int64_t blocks = (n + DN_ROWS - 1) / DN_ROWS;
-    const int64_t cap = grid > 0 ? grid : 1024;
-    if (blocks > cap) blocks = cap;
-    const dim3 g((unsigned)blocks), b(64 * DN_WAVES);
-    const bool vec = d % 2 == 0 && reinterpret_cast<uintptr_t>(X) % 16 == 0;
+    const int ndch = (d + DCH - 1) / DCH;
     unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
-#define ALINK_DN_NEAREST(NT)                                                                                       \
-    do {                                                                                                           \
-        if (vec)                                                                                                   \
-            hipLaunchKernelGGL((dense64_nearest_kernel<NT, true>), g, b, 0, st, X, n, d, img, ninit, k, nblk,      \
-                               ndch, cosine, idx, dist, cnt);                                                      \
-        else                                                                                                       \
-            hipLaunchKernelGGL((dense64_nearest_kernel<NT, false>), g, b, 0, st, X, n, d, img, ninit, k, nblk,     \
-                               ndch, cosine, idx, dist, cnt);                                                      \
-    } while (0)
-    if (nt == 1) ALINK_DN_NEAREST(1);
-    else if (nt == 2) ALINK_DN_NEAREST(2);
-    else if (nt == 4) ALINK_DN_NEAREST(4);
-    else ALINK_DN_NEAREST(8);
-#undef ALINK_DN_NEAREST
+    ALINK_D64_LAUNCH(dense64_nearest_kernel, nt, 1, 2, 4, 8, vec_ok(d, X), row_blocks(n, grid, 1024), st, X, n, d,
+                     img, ninit, k, nblk, ndch, cosine, idx, dist, cnt);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

@@ -21,22 +21,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lane_bcast.h"
+
 namespace {
+
+using lane::bcast_f64;
+using lane::bcast_i64;
 
 constexpr int SP_WAVES = 4;        // waves (rows / work items) per 256-thread workgroup
 constexpr int SP_NB = 4;           // cluster blocks of 64 a lane holds at most (256 clusters per pass)
-
-__device__ __forceinline__ double bcast_f64(double v, int lane) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ int64_t bcast_i64(int64_t v, int lane) {
-    const int lo = __builtin_amdgcn_readlane((int)(v & 0xffffffffll), lane);
-    const int hi = __builtin_amdgcn_readlane((int)(v >> 32), lane);
-    return ((int64_t)hi << 32) | (uint32_t)lo;
-}
 
 // NB: cluster blocks of 64 per pass (kp >= 64 * NB unless NB == SP_NB, where the tail block is guarded);
 // U: entries whose gathers are issued together.

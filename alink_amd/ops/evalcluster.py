@@ -63,9 +63,9 @@ def _hip_kind(rows, k: int):
     if rows.n == 0:
         return None
     if isinstance(rows, krows._Dense64Rows):
-        return "f64" if kd64._use_hip(rows.X, k) else None
+        return "f64" if kd64.use_hip(rows.X, k) else None
     if isinstance(rows, krows._SparseRows):
-        return "csr" if ksp._use_hip(rows.X) else None
+        return "csr" if ksp.use_hip(rows.X) else None
     return None
 
 
@@ -74,7 +74,7 @@ def sorted_work(rows, cid: torch.Tensor, k: int):
     evaluation on the HIP kinds, None on the others."""
     if _hip_kind(rows, k) is None:
         return None
-    return kd64._sorted_work(cid, int(k), ignore_outside=True)
+    return kd64.sorted_work(cid, int(k), ignore_outside=True)
 
 
 def cluster_sums(rows, cid: torch.Tensor, k: int, work=None, grid: int = 0) -> torch.Tensor:
@@ -85,7 +85,7 @@ def cluster_sums(rows, cid: torch.Tensor, k: int, work=None, grid: int = 0) -> t
 def cluster_row_sums(block: torch.Tensor, cid: torch.Tensor, k: int, work=None, grid: int = 0) -> torch.Tensor:
     """fp64 ``[k, 3]``: the columns of ``row_pass``'s block summed per cluster, rows in ascending order."""
     if work is not None and block.shape[0] > 0:
-        return kd64._accumulate_work(block, work, int(k), grid)[:, :3]
+        return kd64.accumulate_work(block, work, int(k), grid)[:, :3]
     return kd64.accumulate(block, cid, int(k), grid, ignore_outside=True)[:, :3]
 
 
@@ -143,7 +143,7 @@ def _row_pass_csr_torch(fm, d: int, cid, mean, cnt, n2, code: int) -> torch.Tens
     n, k = fm.nrows, mean.shape[0]
     dev = fm.val.device
     out = torch.zeros((n, 3), dtype=torch.float64, device=dev)
-    col, val = ksp._clipped(fm, d)                  # entries outside [0, d) are (0, 0.0): they add nothing
+    col, val = ksp.clipped(fm, d)                  # entries outside [0, d) are (0, 0.0): they add nothing
     safe = krows.sparse_view(fm, d, val.to(torch.float64))
     safe.col = col
     Mt = mean.t().contiguous()
@@ -206,7 +206,7 @@ def _row_pass_f64(X, cid, mean, cnt, n2, code: int, grid: int) -> torch.Tensor:
     dev = X.device
     n, d = X.shape
     k = mean.shape[0]
-    img, _, nt, nblk = kd64._centroid_image(mean, 1, dev)       # the COSINE code: plain dots
+    img, _, nt, nblk = kd64.centroid_image(mean, 1, dev)       # the COSINE code: plain dots
     stat = _cluster_records(nblk * nt * 16, mean, cnt, n2)
     out = torch.empty((n, 3), dtype=torch.float64, device=dev)
     _lib.call("alink_evalcluster_rows_f64", X.data_ptr(), n, d, cid.data_ptr(), img.data_ptr(), mean.data_ptr(),
@@ -218,7 +218,7 @@ def _row_pass_csr(fm, d: int, cid, mean, cnt, n2, code: int, grid: int) -> torch
     dev = fm.val.device
     n = fm.nrows
     k = mean.shape[0]
-    kp = ksp._kp(k)
+    kp = ksp.kp(k)
     Mt = torch.zeros((d, kp), dtype=torch.float64, device=dev)
     Mt[:, :k] = mean.t()
     stat = _cluster_records(kp, mean, cnt, n2)

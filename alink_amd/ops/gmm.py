@@ -122,9 +122,10 @@ def em_step_torch(X0, mu0, W, logdet, rank, logw):
 
 def _em_image(mu0, W, logdet, rank, logw, dev):
     """The E pass's parameters: the columns of every W_j as a [k dpad, d] matrix (dpad = d rounded up to 16, zero
-    columns behind d) in the lane order of ``kmeans_dense64._centroid_image`` at one tile per block, laid out
-    img [tile, dch, u = 2, g = 4, m = 16, s = 4] (element: column ``tile * 16 + m``, dim ``dch * 32 + 16 u + 4 g + s``)
-    and padded with zero tiles to whole staging groups; ninit = -C_j per column (0 on the padding); cst [k]."""
+    columns behind d) in the lane order of ``kmeans_dense64.centroid_image`` at one tile per block, laid out
+    img [tile, dch, u = 2, g = 4, m = 16, s = 4] (element: column ``tile * 16 + m``, dim ``dch * 32 + 16 u + 4 g + s``;
+    the tile-outermost variant that the layout note of ``csrc/dense64_mfma.h`` sets apart) and padded with zero tiles
+    to whole staging groups; ninit = -C_j per column (0 on the padding); cst [k]."""
     k, d = mu0.shape
     tpc = (d + 15) // 16
     ndch = (d + 31) // 32

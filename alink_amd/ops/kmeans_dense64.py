@@ -31,7 +31,9 @@ from . import _lib
 from .kmeans_sparse import DENSE_DMAX
 
 __all__ = ["ACCUM_ROWS", "dense64_supported", "dense64_selected", "nearest", "nearest_counts", "accumulate",
-           "assign_accumulate", "nearest_torch", "assign_accumulate_torch"]
+           "assign_accumulate", "nearest_torch", "assign_accumulate_torch",
+           # shared with ops/evalcluster.py, ops/sos.py, ops/gmm.py and ops/kmeans_rows.py (csrc/dense64_mfma.h)
+           "use_hip", "tiles", "centroid_image", "sorted_work", "accumulate_work"]
 
 ACCUM_ROWS = 256        # rows of one cluster that one wave sums; longer clusters are split and merged in order
 DENSE64_CALLS = 0       # launches of the HIP dense fp64 path (tests read it)
@@ -51,7 +53,9 @@ def dense64_selected(X, k: int) -> bool:
     return dense64_supported(X, k) and os.environ.get("ALINK_KMEANS_DENSE64", "") != "0"
 
 
-def _use_hip(X: torch.Tensor, k: int) -> bool:
+def use_hip(X: torch.Tensor, k: int) -> bool:
+    """Whether these rows go to the HIP kernels of the dense fp64 tile loop (``csrc/dense64_mfma.h``): False on the
+    CPU, an error for GPU rows the kernels do not take, else whether the kernel library is enabled."""
     if not X.is_cuda:
         return False
     if not dense64_supported(X, k):
@@ -116,21 +120,24 @@ def assign_accumulate_torch(X: torch.Tensor, C: torch.Tensor, chunk: int = TORCH
 # ---------------------------------------------------------------------------------------------------
 # HIP path
 # ---------------------------------------------------------------------------------------------------
-def _tiles(k: int) -> int:
-    """Centroid tiles of 16 per block: the power of two that covers k, at most NT_MAX."""
+def tiles(k: int) -> int:
+    """Tiles of 16 table rows per block of the image (NT of ``csrc/dense64_mfma.h``): the power of two that covers
+    k, at most NT_MAX."""
     nt = 1
     while nt < NT_MAX and 16 * nt < k:
         nt *= 2
     return nt
 
 
-def _centroid_image(C: torch.Tensor, cosine: int, dev):
-    """The centroids in the order the nearest kernel's lanes read them, zero-padded to whole blocks of 16 nt
-    centroids and whole chunks of 32 dims: img [nblk, ndch, u = 2, nt, g = 4, m = 16, s = 4] where the element is
-    centroid ``(blk * nt + t) * 16 + m``, dim ``dch * 32 + 16 u + 4 g + s``; and the accumulator start
-    ninit [nblk * 16 nt] = -|c|^2/2 (0 for COSINE and on the padded slots)."""
+def centroid_image(C: torch.Tensor, cosine: int, dev):
+    """The lane-ordered image of the table ``C`` [k, d] that every kernel of the dense fp64 tile loop stages in LDS;
+    the layout and the operand maps it serves are described once, in ``csrc/dense64_mfma.h``.  Returns
+    ``(img, ninit, nt, nblk)``: the rows zero-padded to ``nblk`` whole blocks of 16 ``nt = tiles(k)`` rows and whole
+    chunks of 32 dims, img [nblk, ndch, u = 2, nt, g = 4, m = 16, s = 4] where the element is row
+    ``(blk * nt + t) * 16 + m``, dim ``dch * 32 + 16 u + 4 g + s``; and the accumulator start
+    ninit [nblk * 16 nt] = -|c|^2/2 (0 for COSINE, ``cosine = 1``, and on the padded slots)."""
     k, d = C.shape
-    nt = _tiles(k)
+    nt = tiles(k)
     nblk = (k + 16 * nt - 1) // (16 * nt)
     ndch = (d + 31) // 32
     Cd = C.to(device=dev, dtype=torch.float64)
@@ -156,7 +163,7 @@ def _nearest_hip(X: torch.Tensor, C: torch.Tensor, dist_type: str, want_idx: boo
     counts = torch.zeros(k, dtype=torch.int64, device=dev) if want_counts else None
     if n == 0:      # nothing is launched for an empty partition
         return idx, dist, counts
-    img, ninit, nt, nblk = _centroid_image(C, cosine, dev)
+    img, ninit, nt, nblk = centroid_image(C, cosine, dev)
     _lib.call("alink_kmeans_dense64_nearest", X.data_ptr(), n, d, img.data_ptr(), ninit.data_ptr(), k, nt, nblk,
               cosine, idx.data_ptr() if want_idx else None, dist.data_ptr() if want_dist else None,
               counts.data_ptr() if want_counts else None, int(grid), _lib.stream_ptr(dev))
@@ -168,7 +175,7 @@ def nearest(X: torch.Tensor, C: torch.Tensor, dist_type: str, grid: int = 0) -> 
     """Nearest centroid per row: (idx int64 [n], dist fp64 [n]) — squared distance for EUCLIDEAN, ``1 - x.c`` for
     COSINE.  Bit-equal scores go to the lowest centroid index; a row with a NaN goes to index 0."""
     _dist_code(dist_type)
-    if _use_hip(X, C.shape[0]):
+    if use_hip(X, C.shape[0]):
         idx, dist, _ = _nearest_hip(X, C, dist_type, True, True, False, grid)
         return idx.to(torch.int64), dist
     return nearest_torch(X, C, dist_type)
@@ -178,13 +185,14 @@ def nearest_counts(X: torch.Tensor, C: torch.Tensor, dist_type: str, grid: int =
     """Rows per nearest centroid, exact int64 [k] (integer adds on the GPU, no per-row output)."""
     _dist_code(dist_type)
     k = C.shape[0]
-    if _use_hip(X, k):
+    if use_hip(X, k):
         return _nearest_hip(X, C, dist_type, False, False, True, grid)[2]
     return torch.bincount(nearest_torch(X, C, dist_type)[0], minlength=k)
 
 
-def _sorted_work(idx: torch.Tensor, k: int, ignore_outside: bool = False):
-    """The accumulate kernel's work list for the rows' clusters ``idx`` int32 / int64 [n]: one stable sort, then
+def sorted_work(idx: torch.Tensor, k: int, ignore_outside: bool = False):
+    """The work list of the accumulate kernel (``csrc/kmeans_dense64.hip``) for the rows' clusters ``idx`` int32 /
+    int64 [n], shared by KMeans, BisectingKMeans and EvalCluster: one stable sort, then
     (perm, nchunk, wstart, wlen, cfirst, nch, cnt).  Every value must be in [0, k), unless ``ignore_outside``: such
     rows then get the key ``k``, sort behind every cluster, and no chunk covers them (they are never read)."""
     dev = idx.device
@@ -207,8 +215,9 @@ def _sorted_work(idx: torch.Tensor, k: int, ignore_outside: bool = False):
     return perm, nchunk, wstart.contiguous(), wlen.contiguous(), cfirst, nch.contiguous(), cnt.contiguous()
 
 
-def _accumulate_work(X: torch.Tensor, work, k: int, grid: int = 0) -> torch.Tensor:
-    """[k, d+1] of the rows ``X`` [n, d] through a work list of ``_sorted_work`` (one list serves several ``X``)."""
+def accumulate_work(X: torch.Tensor, work, k: int, grid: int = 0) -> torch.Tensor:
+    """[k, d+1] of the rows ``X`` [n, d] through a work list of ``sorted_work`` (one list serves several ``X``), by
+    ``alink_kmeans_dense64_accum``: the same bits for every launch and every ``grid``."""
     global DENSE64_CALLS
     n, d = X.shape
     dev = X.device
@@ -226,7 +235,7 @@ def _accumulate_hip(X: torch.Tensor, idx: torch.Tensor, k: int, grid: int = 0,
                     ignore_outside: bool = False) -> torch.Tensor:
     """[k, d+1] through the cluster-sorted row list; ``idx`` int32 / int64 [n] with every value in [0, k) (or, with
     ``ignore_outside``, the other rows left out and unread)."""
-    return _accumulate_work(X, _sorted_work(idx, k, ignore_outside), k, grid)
+    return accumulate_work(X, sorted_work(idx, k, ignore_outside), k, grid)
 
 
 def accumulate(X: torch.Tensor, idx: torch.Tensor, k: int, grid: int = 0,
@@ -239,7 +248,7 @@ def accumulate(X: torch.Tensor, idx: torch.Tensor, k: int, grid: int = 0,
         raise ValueError("idx must be an [n] tensor")
     if X.shape[0] == 0:
         return torch.zeros((k, X.shape[1] + 1), dtype=torch.float64, device=X.device)
-    if _use_hip(X, k):
+    if use_hip(X, k):
         return _accumulate_hip(X, idx.to(X.device), k, grid, ignore_outside)
     if ignore_outside:
         idx = idx.to(torch.int64)
@@ -255,7 +264,7 @@ def assign_accumulate(X: torch.Tensor, C: torch.Tensor, grid: int = 0) -> torch.
     k = C.shape[0]
     if X.shape[0] == 0:
         return torch.zeros((k, X.shape[1] + 1), dtype=torch.float64, device=X.device)
-    if _use_hip(X, k):
+    if use_hip(X, k):
         idx, _, _ = _nearest_hip(X, C, "EUCLIDEAN", True, False, False, grid)
         return _accumulate_hip(X, idx, k, grid)
     return assign_accumulate_torch(X, C)

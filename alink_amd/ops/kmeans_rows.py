@@ -115,7 +115,7 @@ class Rows:
         """fp64 ``[nslots, d + 2] = [sum_x | count | sum |x|^2]`` of the rows per slot; rows whose slot is outside
         ``[0, nslots)`` add nothing.  ``sqnorm=False`` may leave the last column zero (only the EUCLIDEAN cost reads
         it).  An empty partition launches nothing.  ``work``: the sorted work list of these slots
-        (``kmeans_dense64._sorted_work(slot, nslots, ignore_outside=True)``) where the caller has it already; the
+        (``kmeans_dense64.sorted_work(slot, nslots, ignore_outside=True)``) where the caller has it already; the
         HIP kinds then do not sort again, the torch kinds never sort."""
         if self.n == 0:
             return torch.zeros((int(nslots), self.d + 2), dtype=torch.float64, device=slot.device)
@@ -181,7 +181,7 @@ class _SparseRows(Rows):
     def _dot_chunks(self, C: torch.Tensor):
         """Yields (first row, ``X[s:e] @ C.T`` fp64 [m, k]) in row chunks of the CSR product."""
         fm, d = self.X, self.d
-        col, val = ksp._clipped(fm, d)
+        col, val = ksp.clipped(fm, d)
         safe = sparse_view(fm, d, val)
         safe.col = col
         Ct = C.t().contiguous()
@@ -203,7 +203,7 @@ class _SparseRows(Rows):
         return ksp.row_sqnorm(self.X, self.d)
 
     def _descend(self, table, slot, levels, grid):
-        if ksp._use_hip(self.X):
+        if ksp.use_hip(self.X):
             return bops.descend_csr(self.X, table, slot, levels, grid)
         return _torch_descend(lambda M: torch.cat([dot for _, dot in self._dot_chunks(M)]), table, slot, levels)
 
@@ -212,15 +212,15 @@ class _SparseRows(Rows):
         buf = torch.zeros((nslots, d + 2), dtype=torch.float64, device=fm.device)
         idx = torch.where((slot >= 0) & (slot < nslots), slot, torch.full_like(slot, -1)).to(torch.int32)
         counts = torch.bincount(idx.to(torch.int64) + 1, minlength=nslots + 1)[1:]
-        if ksp._use_hip(fm):
+        if ksp.use_hip(fm):
             buf[:, :d + 1] = ksp.accumulate_hip(fm, idx.contiguous(), nslots, d, counts, grid)
             if sqnorm:      # the per-row norms through the dense accumulate at d = 1: no float atomics here either
                 sq = self.row_sqnorm()[:, None]
                 buf[:, d + 1] = (kd64.accumulate(sq, idx, nslots, grid, ignore_outside=True) if work is None else
-                                 kd64._accumulate_work(sq, work, nslots, grid))[:, 0]
+                                 kd64.accumulate_work(sq, work, nslots, grid))[:, 0]
             return buf
         key = torch.where(idx >= 0, idx, torch.full_like(idx, nslots)).to(torch.int64)      # a spare last slot
-        buf[:, :d + 1] = ksp._accumulate_torch(fm, key, nslots + 1, d)[:nslots]
+        buf[:, :d + 1] = ksp.accumulate_torch(fm, key, nslots + 1, d)[:nslots]
         buf[:, d + 1] = torch.zeros(nslots + 1, dtype=torch.float64, device=fm.device).index_add_(
             0, key, self.row_sqnorm())[:nslots]
         return buf
@@ -321,21 +321,21 @@ class _Dense64Rows(_TorchRows):
         return kd64.nearest_counts(self.X, C, self.dist_type)
 
     def _descend(self, table, slot, levels, grid):
-        if kd64._use_hip(self.X, 1):
+        if kd64.use_hip(self.X, 1):
             return bops.descend_f64(self.X, table, slot, levels, grid)
         return super()._descend(table, slot, levels, grid)
 
     def _child_stats(self, slot, nslots, sqnorm, grid, work=None):
-        if not kd64._use_hip(self.X, nslots):
+        if not kd64.use_hip(self.X, nslots):
             return super()._child_stats(slot, nslots, sqnorm, grid)
         # one stable sort of the slots serves both accumulates; rows without a slot sort last and are not read
         X, d = self.X, self.d
         if work is None:
-            work = kd64._sorted_work(slot, nslots, ignore_outside=True)
+            work = kd64.sorted_work(slot, nslots, ignore_outside=True)
         buf = torch.zeros((nslots, d + 2), dtype=torch.float64, device=X.device)
-        buf[:, :d + 1] = kd64._accumulate_work(X, work, nslots, grid)
+        buf[:, :d + 1] = kd64.accumulate_work(X, work, nslots, grid)
         if sqnorm:
-            buf[:, d + 1] = kd64._accumulate_work(self.row_sqnorm()[:, None], work, nslots, grid)[:, 0]
+            buf[:, d + 1] = kd64.accumulate_work(self.row_sqnorm()[:, None], work, nslots, grid)[:, 0]
         return buf
 
 

@@ -29,7 +29,9 @@ import torch
 from . import _lib
 
 __all__ = ["ACCUM_CHUNK", "sparse_supported", "sparse_selected", "prepare", "nearest", "nearest_counts",
-           "assign_accumulate", "nearest_torch", "assign_accumulate_torch", "row_sqnorm", "take_dense"]
+           "assign_accumulate", "nearest_torch", "assign_accumulate_torch", "row_sqnorm", "take_dense",
+           # shared with ops/evalcluster.py and ops/kmeans_rows.py
+           "use_hip", "clipped", "kp", "accumulate_torch", "nearest_hip"]
 
 ACCUM_CHUNK = 512       # entries of one column that one wave sums; longer columns are split and merged in order
 DENSE_DMAX = 1024       # the largest d a dense HIP KMeans kernel covers (ops/kmeans.py): sparse input wider than
@@ -58,7 +60,9 @@ def sparse_supported(fm) -> bool:
             and fm.nrows < 2 ** 31)
 
 
-def _use_hip(fm) -> bool:
+def use_hip(fm) -> bool:
+    """Whether this matrix goes to the HIP CSR kernels: False on the CPU, an error for a GPU matrix the kernels do
+    not take, else whether the kernel library is enabled."""
     if not fm.val.is_cuda:
         return False
     if not sparse_supported(fm):
@@ -76,7 +80,7 @@ def _dist_code(dist_type: str) -> int:
 # ---------------------------------------------------------------------------------------------------
 # torch path (CPU, oracle)
 # ---------------------------------------------------------------------------------------------------
-def _clipped(fm, d: int):
+def clipped(fm, d: int):
     """(col int64, val) with the entries outside [0, d) turned into (0, 0.0): they then add nothing."""
     col = fm.col.to(torch.int64)
     ok = (col >= 0) & (col < d)
@@ -91,7 +95,7 @@ def row_sqnorm(fm, d: Optional[int] = None) -> torch.Tensor:
     out = torch.zeros(n, dtype=torch.float64, device=fm.val.device)
     if n == 0 or fm.val.numel() == 0 or d == 0:
         return out
-    col, val = _clipped(fm, d)
+    col, val = clipped(fm, d)
     if val.is_cuda and _lib.available():
         from .feature import csr_mv
         return csr_mv(fm.crow, col, val * val, torch.ones(d, dtype=torch.float64, device=val.device))
@@ -130,7 +134,7 @@ def _scores_torch(fm, C: torch.Tensor, cosine: int, chunk: int):
     Cd = C.to(device=fm.val.device, dtype=torch.float64)
     Ct = Cd.t().contiguous()
     cn = (Cd * Cd).sum(1)
-    col, val = _clipped(fm, d)
+    col, val = clipped(fm, d)
     counts = fm.crow[1:] - fm.crow[:-1]
     n = fm.nrows
     for s in range(0, n, chunk):
@@ -161,13 +165,15 @@ def nearest_torch(fm, C: torch.Tensor, dist_type: str, chunk: int = TORCH_CHUNK)
     return idx, dist
 
 
-def _accumulate_torch(fm, idx: torch.Tensor, k: int, d: int) -> torch.Tensor:
+def accumulate_torch(fm, idx: torch.Tensor, k: int, d: int) -> torch.Tensor:
+    """Torch path of the per-cluster sums: [k, d+1] fp64 ``[sum_x | count]`` of the rows' clusters ``idx`` int64 [n]
+    (every value in [0, k))."""
     buf = torch.zeros((k, d + 1), dtype=torch.float64, device=fm.val.device)
     if fm.nrows == 0:
         return buf
     buf[:, d] = torch.bincount(idx, minlength=k).to(torch.float64)
     if fm.val.numel():
-        col, val = _clipped(fm, d)
+        col, val = clipped(fm, d)
         buf.view(-1).index_add_(0, idx[fm.row_ids()] * (d + 1) + col, val.to(torch.float64))
     return buf
 
@@ -176,30 +182,34 @@ def assign_accumulate_torch(fm, C: torch.Tensor, dist_type: str, chunk: int = TO
     """Torch reference of ``assign_accumulate``: [k, d+1] fp64 ``[sum_x | count]`` of the nearest-centroid
     assignment; on the CPU every (cluster, column) sum runs in ascending row order."""
     k, d = C.shape
-    return _accumulate_torch(fm, nearest_torch(fm, C, dist_type, chunk)[0], k, d)
+    return accumulate_torch(fm, nearest_torch(fm, C, dist_type, chunk)[0], k, d)
 
 
 # ---------------------------------------------------------------------------------------------------
 # HIP path
 # ---------------------------------------------------------------------------------------------------
-def _kp(k: int) -> int:
+def kp(k: int) -> int:
+    """k padded to the cluster blocks of the CSR kernels: a multiple of 64, at least 64 (the ``kp`` of
+    ``csrc/kmeans_sparse.hip`` and ``csrc/evalcluster.hip``)."""
     return max(64, (int(k) + 63) // 64 * 64)
 
 
 def _centroid_operands(C: torch.Tensor, cosine: int, dev):
     """Ct [d, kp] fp64 (transposed, zero-padded) and the score offsets cn [kp] (+inf on the padded clusters)."""
     k, d = C.shape
-    kp = _kp(k)
+    kpad = kp(k)
     Cd = C.to(device=dev, dtype=torch.float64)
-    Ct = torch.zeros((d, kp), dtype=torch.float64, device=dev)
+    Ct = torch.zeros((d, kpad), dtype=torch.float64, device=dev)
     Ct[:, :k] = Cd.t()
-    cn = torch.full((kp,), float("inf"), dtype=torch.float64, device=dev)
+    cn = torch.full((kpad,), float("inf"), dtype=torch.float64, device=dev)
     cn[:k] = 0.0 if cosine else (Cd * Cd).sum(1)
-    return Ct, cn, kp
+    return Ct, cn, kpad
 
 
-def _nearest_hip(fm, C: torch.Tensor, dist_type: str, want_idx: bool, want_dist: bool, want_counts: bool,
+def nearest_hip(fm, C: torch.Tensor, dist_type: str, want_idx: bool, want_dist: bool, want_counts: bool,
                  grid: int = 0):
+    """``alink_kmeans_sparse_nearest`` with the outputs the caller asks for: (idx int32 [n], dist fp64 [n],
+    counts int64 [kp(k)]), each None unless wanted.  Nothing is launched for an empty matrix."""
     global SPARSE_CALLS
     cosine = _dist_code(dist_type)
     dev = fm.val.device
@@ -207,20 +217,20 @@ def _nearest_hip(fm, C: torch.Tensor, dist_type: str, want_idx: bool, want_dist:
     n = fm.nrows
     idx = torch.zeros(n, dtype=torch.int32, device=dev) if want_idx else None
     dist = torch.zeros(n, dtype=torch.float64, device=dev) if want_dist else None
-    kp = _kp(k)
-    counts = torch.zeros(kp, dtype=torch.int64, device=dev) if want_counts else None
+    kpad = kp(k)
+    counts = torch.zeros(kpad, dtype=torch.int64, device=dev) if want_counts else None
     if n == 0:      # nothing is launched for an empty partition
         return idx, dist, counts
     if k < 1 or d < 1:
         raise ValueError("sparse KMeans needs at least one centroid and one column")
-    Ct, cn, kp = _centroid_operands(C, cosine, dev)
+    Ct, cn, kpad = _centroid_operands(C, cosine, dev)
     crow = fm.crow.contiguous()
     col = fm.col.contiguous()
     val = fm.val.contiguous()
     if int(crow.numel()) != n + 1 or col.numel() != val.numel():
         raise ValueError("malformed CSR matrix")
     _lib.call("alink_kmeans_sparse_nearest", crow.data_ptr(), col.data_ptr(), int(col.dtype == torch.int64),
-              val.data_ptr(), n, d, Ct.data_ptr(), cn.data_ptr(), kp, 1.0 if cosine else 2.0, cosine,
+              val.data_ptr(), n, d, Ct.data_ptr(), cn.data_ptr(), kpad, 1.0 if cosine else 2.0, cosine,
               idx.data_ptr() if want_idx else None, dist.data_ptr() if want_dist else None,
               counts.data_ptr() if want_counts else None, int(grid), _lib.stream_ptr(dev))
     SPARSE_CALLS += 1
@@ -230,8 +240,8 @@ def _nearest_hip(fm, C: torch.Tensor, dist_type: str, want_idx: bool, want_dist:
 def nearest(fm, C: torch.Tensor, dist_type: str, grid: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """Nearest centroid per row: (idx int64 [n], dist fp64 [n]) — squared distance for EUCLIDEAN, ``1 - x.c`` for
     COSINE.  Equal scores go to the lowest centroid index; an empty row takes ``argmin |c|^2``."""
-    if _use_hip(fm):
-        idx, dist, _ = _nearest_hip(fm, C, dist_type, True, True, False, grid)
+    if use_hip(fm):
+        idx, dist, _ = nearest_hip(fm, C, dist_type, True, True, False, grid)
         return idx.to(torch.int64), dist
     return nearest_torch(fm, C, dist_type)
 
@@ -239,8 +249,8 @@ def nearest(fm, C: torch.Tensor, dist_type: str, grid: int = 0) -> Tuple[torch.T
 def nearest_counts(fm, C: torch.Tensor, dist_type: str, grid: int = 0) -> torch.Tensor:
     """Rows per nearest centroid, exact int64 [k] (integer atomics on the GPU, no per-row output)."""
     k = C.shape[0]
-    if _use_hip(fm):
-        return _nearest_hip(fm, C, dist_type, False, False, True, grid)[2][:k]
+    if use_hip(fm):
+        return nearest_hip(fm, C, dist_type, False, False, True, grid)[2][:k]
     return torch.bincount(nearest_torch(fm, C, dist_type)[0], minlength=k)
 
 
@@ -310,12 +320,12 @@ def accumulate_hip(fm, idx: torch.Tensor, k: int, d: int, counts: Optional[torch
     csc = prepare(fm, d)
     if csc.nwork == 0:
         return buf
-    kp = _kp(k)
-    sumT = torch.zeros((d, kp), dtype=torch.float64, device=dev)
-    part = torch.empty((max(csc.nslots, 1), kp), dtype=torch.float64, device=dev)
+    kpad = kp(k)
+    sumT = torch.zeros((d, kpad), dtype=torch.float64, device=dev)
+    part = torch.empty((max(csc.nslots, 1), kpad), dtype=torch.float64, device=dev)
     _lib.call("alink_kmeans_sparse_accum", csc.rows.data_ptr(), csc.vals.data_ptr(), idx.data_ptr(), csc.nwork,
               csc.wcol.data_ptr(), csc.wstart.data_ptr(), csc.wlen.data_ptr(), csc.wslot.data_ptr(), csc.nmulti,
-              csc.mcol.data_ptr(), csc.mfirst.data_ptr(), csc.mcount.data_ptr(), kp, sumT.data_ptr(),
+              csc.mcol.data_ptr(), csc.mfirst.data_ptr(), csc.mcount.data_ptr(), kpad, sumT.data_ptr(),
               part.data_ptr(), int(grid), _lib.stream_ptr(dev))
     SPARSE_CALLS += 1
     buf[:, :d] = sumT[:, :k].t()
@@ -325,7 +335,7 @@ def accumulate_hip(fm, idx: torch.Tensor, k: int, d: int, counts: Optional[torch
 def assign_accumulate(fm, C: torch.Tensor, dist_type: str, grid: int = 0) -> torch.Tensor:
     """The Lloyd step's ``[k, d+1]`` fp64 buffer ``[sum_x | count]`` for this rank's sparse rows."""
     k, d = C.shape
-    if _use_hip(fm):
-        idx, _, counts = _nearest_hip(fm, C, dist_type, True, False, True, grid)
+    if use_hip(fm):
+        idx, _, counts = nearest_hip(fm, C, dist_type, True, False, True, grid)
         return accumulate_hip(fm, idx, k, d, counts, grid)
     return assign_accumulate_torch(fm, C, dist_type)

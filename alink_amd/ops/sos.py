@@ -19,7 +19,7 @@ squared row norms: ``D_ij = max(0, (q_i + q_j) - 2 x_i . x_j)``, the pair ``j ==
   With a GPU present a missing kernel library raises, unless ``ALINK_ALLOW_TORCH_FALLBACK=1``.
 
 On the GPU no ``[n, n]`` or ``[block, n]`` buffer exists: scratch is the centred rows, their lane-ordered image
-(``kmeans_dense64._centroid_image``, d padded to 32) and a few ``[n]`` vectors.  No float atomics: the same bits for
+(``kmeans_dense64.centroid_image``, d padded to 32) and a few ``[n]`` vectors.  No float atomics: the same bits for
 every launch, every ``grid`` and every split into ``rows=`` / ``cols=`` ranges (so a multi-rank split is an
 all-gather of two vectors).
 """
@@ -32,7 +32,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .kmeans_dense64 import _centroid_image
+from .kmeans_dense64 import centroid_image
 
 __all__ = ["SOS_MAX_D", "SOS_DMAX", "MAX_ITER", "TOL", "sos_supported", "sos_selected", "search", "products", "scores",
            "search_torch", "products_torch"]
@@ -173,7 +173,7 @@ def _prepare(X: torch.Tensor):
         raise ValueError(f"the SOS kernels need contiguous fp64 [n, d] GPU rows with n >= 2 and 1 <= d <= {SOS_DMAX}")
     _lib.require()
     Xc, q = _centre(X)
-    img, qpad, nt, nblk = _centroid_image(Xc, 1, Xc.device)      # cosine = 1: the zero vector of the slots
+    img, qpad, nt, nblk = centroid_image(Xc, 1, Xc.device)      # cosine = 1: the zero vector of the slots
     qpad[:q.shape[0]] = q
     return Xc, img, qpad, nt, nblk
 

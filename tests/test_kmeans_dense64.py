@@ -113,3 +113,50 @@ def test_cpu_rows_keep_the_torch_result_bit_for_bit():
     got = kops.assign_accumulate(X, C)
     assert kd.DENSE64_CALLS == calls
     assert torch.equal(got, kops.assign_accumulate_torch(X, C))
+
+
+# (k, d) -> the documented (nt, nblk): nt the power of two whose 16 nt rows cover k, at most 8; nblk blocks of 16 nt.
+# nt = 1, 2, 4, 8, more than one block, an odd d and a dim chunk edge (d = 32 fills a chunk, d = 34 spills over)
+@pytest.mark.parametrize("k,d,nt_doc,nblk_doc", [(1, 1, 1, 1), (5, 7, 1, 1), (17, 32, 2, 1), (40, 34, 4, 1),
+                                                 (300, 64, 8, 3)])
+def test_centroid_image_layout(k, d, nt_doc, nblk_doc):
+    """The Python end of the image contract of ``csrc/dense64_mfma.h``: element [blk, dch, u, t, g, m, s] of the
+    image is C[(blk * nt + t) * 16 + m, dch * 32 + 16 u + 4 g + s], or 0 outside C — checked index by index, not by the
+    permute that builds it; ninit is -|c|^2 / 2 summed over the padded rows, bit for bit, and 0 on padded slots and
+    for COSINE."""
+    import math
+    from alink_amd.ops import kmeans_dense64 as kd
+    rng = np.random.default_rng(100 * k + d)
+    C = rng.normal(size=(k, d))
+    if k > 3:
+        C[2] = C[3] = C[1]          # duplicate rows, odd and even: the same bits of |c|^2 wherever a row starts
+    ndch = (d + 31) // 32
+    for cosine in (0, 1):
+        img, ninit, nt, nblk = kd.centroid_image(torch.from_numpy(C), cosine, "cpu")
+        assert kd.tiles(k) == nt == nt_doc and nblk == nblk_doc
+        assert img.dtype == torch.float64 and img.is_contiguous()
+        assert tuple(img.shape) == (nblk, ndch, 2, nt, 4, 16, 4)
+        got = img.numpy()
+        pad = np.full((nblk * nt * 16, ndch * 32), np.nan)          # the padded rows, built by the same index loop
+        for blk, dch, u, t, g, m, s in np.ndindex(*got.shape):
+            r, j = (blk * nt + t) * 16 + m, dch * 32 + 16 * u + 4 * g + s
+            want = C[r, j] if r < k and j < d else 0.0
+            assert got[blk, dch, u, t, g, m, s] == want, (blk, dch, u, t, g, m, s)
+            pad[r, j] = want
+        ni = ninit.numpy()
+        assert ni.dtype == np.float64 and ni.shape == (nblk * nt * 16,)
+        assert not ni[k:].any()                                     # exactly 0 on the padded slots
+        if cosine:
+            assert not ni.any()
+            continue
+        # -|c|^2 / 2 taken from the padded rows, bit for bit: the summation order is that of a padded row, whatever
+        # the alignment of the row in C
+        padt = torch.from_numpy(pad)
+        assert np.array_equal(ni, (-0.5 * (padt * padt).sum(1)).numpy())
+        for r in range(k):
+            # independently: any order of the d (+ zero padding) fp64 additions is within d ulp-halves of the exact
+            # sum of squares
+            exact = math.fsum(float(v) * float(v) for v in C[r])
+            assert abs(ni[r] + 0.5 * exact) <= 0.5 * exact * (d + 1) * 2.0 ** -53, r
+        if k > 3:
+            assert ni[2] == ni[1] and ni[3] == ni[1]

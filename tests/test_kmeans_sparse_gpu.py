@@ -150,7 +150,7 @@ def test_accumulate(k, integer):
     assert csc.nmulti >= 1 and int(csc.mcount.max()) == 3           # column 0 spans three chunks
     assert ksp.prepare(fm) is csc                                    # built once
     C = torch.from_numpy(np.random.default_rng(k).normal(size=(k, d))).cuda()
-    idx, _, counts = ksp._nearest_hip(fm, C, "EUCLIDEAN", True, False, True)
+    idx, _, counts = ksp.nearest_hip(fm, C, "EUCLIDEAN", True, False, True)
     buf = ksp.accumulate_hip(fm, idx, k, d, counts)
     idx_h = idx.cpu().to(torch.int64)
     Xd = torch.from_numpy(dense)

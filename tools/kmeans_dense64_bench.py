@@ -112,7 +112,7 @@ def main():
         t_nd, t_od = ab(new_dist, old_dist, a.reps)
         t_cnt = [timed(new_counts) for _ in range(a.reps)]
         t_pred = [timed(new_predict) for _ in range(a.reps)]
-        nt = kd._tiles(k)
+        nt = kd.tiles(k)
         kpad = (k + 16 * nt - 1) // (16 * nt) * 16 * nt
         dpad = (d + 31) // 32 * 32
         step_bytes = 2.0 * n * d * 8                    # the rows are read by the nearest pass and by the sums

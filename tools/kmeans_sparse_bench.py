@@ -85,7 +85,7 @@ def main():
     state = {}
 
     def nearest():
-        state["idx"], _, state["cnt"] = ksp._nearest_hip(fm, C, a.dist, True, False, True)
+        state["idx"], _, state["cnt"] = ksp.nearest_hip(fm, C, a.dist, True, False, True)
 
     def accum():
         state["buf"] = ksp.accumulate_hip(fm, state["idx"], a.k, a.d, state["cnt"])
