@@ -1,7 +1,6 @@
 #!/bin/bash
 # Build A/B variants of the v10 KMeans kernel into variants/libalink_hip_<name>.so (the in-tree lib's other
 # objects + a variant kmeans_v10.o), for tools/kmeans_ab.py.  Run after `python build_native.py`.
-#   pair     : -DKM10_PAIRMAX=1 (both distance tiles of a pair in one MFMA stage loop)
 #   timing   : -DKM10_TIMING=1 (per-workgroup stamps and per-role wait sums; tools/kmeans_wg_timing.py).
 #              `... timing` builds only this one
 #   pfd      : -DKM10_PFD=1 (the ALINK_KMEANS_V10_PFD L2 prefetch A/B; `... pfd` builds only this one)
@@ -21,6 +20,5 @@ build_var() {
 [ "$1" = timing ] && { build_var timing "-DKM10_TIMING=1"; exit 0; }
 [ "$1" = pfd ] && { build_var pfd "-DKM10_PFD=1"; exit 0; }
 [ -n "$1" ] && { build_var "$1" "$2"; exit 0; }
-build_var pair "-DKM10_PAIRMAX=1"
 build_var timing "-DKM10_TIMING=1"
 build_var pfd "-DKM10_PFD=1"
