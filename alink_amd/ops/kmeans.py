@@ -111,10 +111,12 @@ KERNEL_VERSIONS = ("v7", "v10")
 # v7 variant (csrc/kmeans_v7.hip VAR): 0 = all 8 waves stage the tile ring; 1 (default) = the accumulate waves
 # stage it all, so the distance waves (the critical role) carry no LDS-DMA issue cost or vmcnt waits
 V7_VAR = int(os.environ.get("ALINK_KMEANS_V7_VAR", "1"))
-# v10 launch flags (csrc/kmeans_v10.hip mode bit 4): 1 (default) = default-policy X loads, 0 = non-temporal.
-# Under the full kernel the default policy measured 2-5 % faster on every box (profiles/kmeans_v10_r3.txt),
-# although the load pipeline alone streams faster with nt
-V10_FLAGS = int(os.environ.get("ALINK_KMEANS_V10_FLAGS", "1"))
+# v10 launch flags (csrc/kmeans_v10.hip mode bit 4): 0 (default) = non-temporal X loads, the kernel's own default;
+# 1 = default-policy loads.  The load pipeline alone always streamed faster with nt (3.77 against 4.03 ms for
+# 25.6 GB).  The full kernel used to be 2-5 % faster with the default policy (profiles/kmeans_v10_r3.txt), which is
+# why 1 was the default; since the accumulate and distance roles were shortened it is the other way round: nt is
+# 2-3 % faster in the kernel bench and in every bench.py pair (profiles/kmeans_v10_sweep.txt)
+V10_FLAGS = int(os.environ.get("ALINK_KMEANS_V10_FLAGS", "0"))
 V10_KMAX = 112
 # serpentine tile order across Lloyd supersteps (serpentine_reverse)
 SERPENTINE = os.environ.get("ALINK_KMEANS_SERPENTINE", "1") != "0"

@@ -6,9 +6,15 @@ One data set, several launch configurations in one process (data generation of 1
 python tools/kmeans_kernel_bench.py --rows 100000000 --k 100 --iters 10 \
     --configs v7:0,v10:0,v10:1,v10:2 --modes 0,1,2 --sub-rows 12500000
 
-A config is ``kernel:flags`` (v7 flags = DMA variant bits 4-5, v10 flags = 1 non-temporal loads, 2 nine-slot
-ring); modes are 0 full, 1 load pipeline only, 2 compute only.  ``--sub-rows`` also times the first R rows
-(the per-rank shape of an 8-GPU job).  Prints one JSON line per (rows, config, mode).
+A config is ``kernel:flags``.  v7 flags are the DMA variant (mode bits 4-5).  v10 flags: 1 = default-policy X
+loads; 0 = what ``ALINK_KMEANS_V10_FLAGS`` says, which is non-temporal loads unless it is set to 1.  Modes are
+0 full, 1 load pipeline only, 2 compute only.  ``--sub-rows`` also times the first R rows (the per-rank shape of
+an 8-GPU job).  Prints one JSON line per (rows, config, mode).
+
+``--b2b N`` also times N launches issued back to back with the serpentine direction alternating, between two
+events and with no synchronisation inside -- the way bench.py runs the kernel (``b2b_ms`` = ms per launch; the first
+pass of the timed run starts on the window the warm-up pass read last).  ``ms`` is the median of single forward
+launches with a synchronisation around each.
 """
 import argparse
 import json
@@ -33,6 +39,7 @@ def main():
     ap.add_argument("--grid", type=int, default=None)
     ap.add_argument("--configs", type=str, default="v10:0")
     ap.add_argument("--modes", type=str, default="0")
+    ap.add_argument("--b2b", type=int, default=0, help="also time this many back-to-back alternating launches")
     a = ap.parse_args()
     dev = torch.device("cuda")
     n, d, k = a.rows, 128, a.k
@@ -94,6 +101,17 @@ def main():
                 t = sorted(times)[len(times) // 2]
                 res.update({"ms": round(t * 1e3, 4), "rows_per_s": rows / t, "TBps": rows * d * 2 / t / 1e12,
                             "min_ms": round(min(times) * 1e3, 4)})
+                if a.b2b > 0:
+                    mm = m | (int(flags) << 4)
+                    K.assign_accumulate_hip(Xs, C, grid=a.grid, mode=mm, reverse=True)      # warm-up, backwards
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record()
+                    for i in range(a.b2b):
+                        K.assign_accumulate_hip(Xs, C, grid=a.grid, mode=mm, reverse=i % 2 == 1)
+                    e1.record()
+                    e1.synchronize()
+                    res.update({"b2b": a.b2b, "b2b_ms": round(e0.elapsed_time(e1) / a.b2b, 4)})
                 print(json.dumps(res), flush=True)
     os.environ.pop("ALINK_KMEANS_KERNEL", None)
     os.environ.pop("ALINK_KMEANS_V10_PFD", None)
