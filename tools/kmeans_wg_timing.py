@@ -63,7 +63,7 @@ def main():
             raw = stamps[:32 * grid].view(torch.int64).view(grid, 16).cpu().numpy().astype(np.float64)
             st = raw[:, :8] * 0.01  # us
             # per-role wait split (shader-clock cycles of wave 0 / wave 4, summed over the launch): the share of
-            # the main loop spent in pre(j)'s vmcnt wait and in its barrier
+            # the main loop spent in sync(j)'s vmcnt wait and in its barrier
             waits = {}
             for role, o in (("dist", 8), ("acc", 11)):
                 loop = np.maximum(raw[:, o + 2], 1.0)
