@@ -14,6 +14,13 @@ counts, and the distinct encoded database is shared; rank r mines the patterns w
 the least frequent item of the pattern; PrefixSpan: the first item) belongs to its item group, and the
 pattern lists are all-gathered — the same partition-by-item decomposition as the reference's parallel
 FP-growth, with no pattern mined twice.
+
+Device path (``fp_growth_device``, ``ops/fpm.py``): the same frequent itemsets counted level by level on vertical
+bitmaps by HIP kernels.  Each rank keeps its own transactions; only the distinct items with their counts, and each
+level's integer candidate counts, cross ranks.  ``fp_growth`` stays the CPU path, the fallback and the oracle.
+Known difference: the device path splits the items column as Java's ``String.split`` does, which drops trailing empty
+items (``"A,B,"`` holds A and B, as in the reference); ``FpGrowthBatchOp``'s host path uses Python's ``split``, which
+keeps them (A, B and the empty item).
 """
 from __future__ import annotations
 
@@ -23,7 +30,7 @@ from typing import Dict, List, Sequence, Tuple
 
 from ...parallel import comm
 
-__all__ = ["fp_growth", "association_rules", "prefix_span", "sequence_rules"]
+__all__ = ["fp_growth", "fp_growth_device", "patterns_dict", "association_rules", "prefix_span", "sequence_rules"]
 
 
 def _min_support(n: int, count: int, percent: float) -> int:
@@ -93,6 +100,117 @@ def fp_growth(transactions: Sequence[Sequence[str]], min_support_count: int, min
     for part in comm.all_gather_object(out):
         patterns.update(part)
     return names, patterns, n, {index[it]: c for it, c in qualified}
+
+
+def fp_growth_device(block, min_support_count: int, min_support_percent: float, max_pattern_length: int,
+                     backend=None, budget=None, pair_max_items=None, stats=None):
+    """``fp_growth`` of this rank's items column (a packed ``StringBlock``) on the block's device with no per-row
+    Python: returns ``(item names by index, (items int32, lens int64, sups int64), N, item supports)`` -- the
+    patterns as the columns of ``ops.fpm.mine``, ``(len, tuple)`` ascending -- or None when the rows cannot be
+    decided from bytes (on any rank): the caller then takes the host path.
+
+    A row is an empty transaction when it is NULL or every byte is ASCII whitespace (0x09-0x0d, 0x1c-0x20); it still
+    counts in N.  A row with no ASCII non-whitespace byte but some byte >= 0x80 may be Unicode whitespace only, which
+    Python's ``strip()`` knows and the bytes do not tell: such a row, and a hash collision in ``unique_ids``, give
+    None.  Items are split by ``ops.strings.split_tokens`` (Java ``String.split``), encoded by ``unique_ids``,
+    de-duplicated per row and counted in torch.  Only the distinct items and their counts come to the host (one
+    ``all_gather_object``), where the rule of ``fp_growth`` orders the qualifying ones; a lookup table maps local ids
+    to ranks.  Every rank keeps its transactions: each level all-reduces its candidate counts.
+
+    Known difference: ``split_tokens`` drops trailing empty items (``"A,B,"`` holds A and B) as the reference's
+    ``String.split`` does; the host path's Python ``split`` keeps them (A, B and the empty item).
+
+    ``backend`` is an ``ops.fpm.Backend`` (default: the kernels on a GPU block, the torch twins on a CPU block);
+    ``stats`` (a list) receives the encode stage's time and then one entry per level from ``ops.fpm.mine``."""
+    import time
+    import torch
+    from ...ops import fpm as F
+    from ...ops.strings import split_tokens, unique_ids
+    dev = block.device
+    t0 = time.perf_counter()
+    if backend is None:
+        backend = F.DEVICE if dev.type == "cuda" else F.TWIN
+    n_local = len(block)
+    d, off = block.data, block.offsets.to(torch.int64)
+    nb = int(d.numel())
+    ws = ((d >= 0x09) & (d <= 0x0d)) | ((d >= 0x1c) & (d <= 0x20))
+    high = d >= 0x80
+
+    def _per_row(mask):
+        cum = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
+        if nb:
+            torch.cumsum(mask.to(torch.int64), 0, out=cum[1:])
+        return cum[off[1:]] - cum[off[:-1]]
+
+    n_high, n_solid = _per_row(high), _per_row(~ws & ~high)
+    empty = (n_solid == 0) & (n_high == 0)
+    if block.nulls is not None:
+        empty |= block.nulls.to(dev)
+    undecided = bool(((n_solid == 0) & (n_high > 0) & ~empty).any())
+    names_local: List[str] = []
+    counts_local: List[int] = []
+    pair = None
+    u = 0
+    if not undecided:
+        tok, doc = split_tokens(block, ord(","))
+        live = ~empty[doc]
+        tok, doc = tok.take(torch.nonzero(live).reshape(-1)), doc[live]
+        enc = unique_ids(tok)
+        if enc is None:
+            undecided = True
+        else:
+            ids, rep = enc
+            u = int(rep.numel())
+            if u:
+                pair = torch.unique(doc * u + ids)                  # distinct (row, item), by row then item id
+                counts_local = torch.bincount(pair % u, minlength=u).cpu().tolist()
+                names_local = tok.take(rep).to_list()
+    counts = Counter()
+    n = 0
+    gathered = comm.all_gather_object((undecided, names_local, counts_local, n_local))
+    if any(g[0] for g in gathered):
+        return None
+    for _, nm, ct, nl in gathered:
+        counts.update(dict(zip(nm, ct)))
+        n += nl
+    min_sup = _min_support(n, min_support_count, min_support_percent)
+    qualified = [(it, c) for it, c in counts.items() if c >= min_sup]
+    qualified.sort(key=lambda t: (-t[1], t[0]))
+    names = [it for it, _ in qualified]
+    index = {it: i for i, it in enumerate(names)}
+    m = len(names)
+    sup_by_index = {index[it]: c for it, c in qualified}
+    crow = torch.zeros(n_local + 1, dtype=torch.int64, device=dev)
+    item = torch.zeros(0, dtype=torch.int32, device=dev)
+    if m and pair is not None and pair.numel():
+        lut = torch.tensor([index.get(s, -1) for s in names_local], dtype=torch.int64, device=dev)
+        row, r = torch.div(pair, u, rounding_mode="floor"), lut[pair % u]
+        ok = r >= 0
+        key = torch.sort(row[ok] * m + r[ok]).values                # by row, then by rank: ascending within a row
+        row = torch.div(key, m, rounding_mode="floor")
+        torch.cumsum(torch.bincount(row, minlength=n_local), 0, out=crow[1:])
+        item = (key - row * m).to(torch.int32)
+    item_sup = torch.tensor([c for _, c in qualified], dtype=torch.int64, device=dev)
+    if stats is not None:
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        stats.append({"stage": "encode", "seconds": time.perf_counter() - t0, "rows": n_local, "items": m,
+                      "entries": int(item.numel())})
+    cols = F.mine(crow, item, m, item_sup, min_sup, int(max_pattern_length), backend, budget=budget,
+                  pair_max_items=pair_max_items, stats=stats)
+    return names, cols, n, sup_by_index
+
+
+def patterns_dict(cols) -> Dict[Tuple[int, ...], int]:
+    """``{sorted index tuple: support}`` (what ``association_rules`` reads) from the pattern columns of
+    ``fp_growth_device``, in their order."""
+    items, lens, sups = (t.cpu().tolist() for t in cols)
+    out: Dict[Tuple[int, ...], int] = {}
+    p = 0
+    for ln, s in zip(lens, sups):
+        out[tuple(items[p:p + ln])] = s
+        p += ln
+    return out
 
 
 def association_rules(patterns: Dict[Tuple[int, ...], int], n: int, min_confidence: float, min_lift: float,

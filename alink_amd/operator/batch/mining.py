@@ -35,10 +35,65 @@ def _own_block(rows, schema, env, replicated_in):
     return mt
 
 
+def _fpgrowth_device_rows(mt, p, device, backend=None):
+    """``(patterns columns, rule rows)`` of ``FpGrowthBatchOp`` through ``M.fp_growth_device`` on ``device``, or None
+    when the rows send the operator down the host path.  The patterns come as columns (itemset strings assembled from
+    the names' bytes, no per-pattern Python); the rules are ``M.association_rules`` on a dict built from them."""
+    from ...common.strings import StringBlock
+    from ...models.nlp.text import _string_block
+    from ...ops.strings import join_tokens
+    res = M.fp_growth_device(_string_block(mt, p.get("itemsCol"), device), int(p.get("minSupportCount")),
+                             float(p.get("minSupportPercent")), int(p.get("maxPatternLength")), backend=backend)
+    if res is None:
+        return None
+    names, (items, lens, sups), n, _ = res
+    dev = items.device
+    P = int(lens.numel())
+    if P:
+        tok = StringBlock.from_list(names, device=dev).take(items.to(torch.int64))
+        doc = torch.repeat_interleave(torch.arange(P, device=dev), lens, output_size=int(items.numel()))
+        sets = join_tokens(tok, doc, torch.ones(int(items.numel()), dtype=torch.bool, device=dev), P,
+                           sep=ord(ITEM_SEP)).to("cpu")
+    else:
+        sets = StringBlock.empty()
+    pcols = [Column(sets), Column(sups.cpu()), Column(lens.cpu())]
+    pats = M.patterns_dict((items, lens, sups))
+    rules = M.association_rules(pats, n, float(p.get("minConfidence")), float(p.get("minLift")),
+                                int(p.get("maxConsequentLength")))
+    rules.sort(key=lambda r: (len(r[0]) + len(r[1]), r[0], r[1]))
+    rrow = [(ITEM_SEP.join(names[i] for i in a) + RULE_SEP + ITEM_SEP.join(names[i] for i in c), len(a) + len(c),
+             float(lift), float(sup), float(conf), int(cnt)) for a, c, cnt, lift, sup, conf in rules]
+    return pcols, rrow
+
+
 class FpGrowthBatchOp(BatchOperator):
+    """Frequent itemsets (output) and association rules (side output 0).  On a GPU the itemsets are mined by
+    ``M.fp_growth_device`` (``ops.fpm.device_selected``; ``ALINK_FPGROWTH_HIP=0`` turns it off); the host path below
+    is the CPU path and the fallback for rows the device path cannot decide."""
+
+    PATTERN_SCHEMA = "itemset string, supportcount bigint, itemcount bigint"
+    RULE_SCHEMA = ("rule string, itemcount bigint, lift double, support_percent double, confidence_percent double, "
+                   "transaction_count bigint")
+
     def linkFrom(self, *inputs):
         mt = self.checkAndGetFirst(inputs).getOutputTable()
         p = self.resolvedParams()
+        from ...ops import fpm as FPM
+        n_rows = mt.num_rows
+        if comm.get_world_size() > 1 and torch.device(self.env.device).type == "cuda":
+            n_rows = sum(comm.all_gather_object(n_rows))        # every rank takes the same path
+        if FPM.device_selected(self.env.device, n_rows):
+            res = _fpgrowth_device_rows(mt, p, self.env.device)
+            if res is not None:         # None: rows that cannot be decided from bytes take the host path below
+                from ...common.table import schema_str_to_schema
+                pcols, rrow = res
+                rep = mt.replicated
+                out = MTable(schema_str_to_schema(self.PATTERN_SCHEMA), pcols)
+                if comm.get_world_size() > 1 and not rep:
+                    out = out.slice(*partition_bounds(out.num_rows, self.env))
+                self.setOutputTable(out)
+                self.setSideOutputTables([_own_block(rrow, self.RULE_SCHEMA, self.env, rep)])
+                return self
         items = mt.col(p.get("itemsCol")).to_list()
         tx = [s.split(ITEM_SEP) if s is not None and s.strip() else [] for s in items]
         names, pats, n, _ = M.fp_growth(tx, int(p.get("minSupportCount")), float(p.get("minSupportPercent")),
