@@ -21,6 +21,11 @@ level's integer candidate counts, cross ranks.  ``fp_growth`` stays the CPU path
 Known difference: the device path splits the items column as Java's ``String.split`` does, which drops trailing empty
 items (``"A,B,"`` holds A and B, as in the reference); ``FpGrowthBatchOp``'s host path uses Python's ``split``, which
 keeps them (A, B and the empty item).
+
+``prefix_span_device`` (``ops/prefixspan.py``) is the same for sequences: one bit field per sequence, S-step and
+I-step support counts by ``alink_fpm_seq_counts``, candidates level by level.  It returns the pattern set and the
+supports of ``prefix_span`` exactly, and declines (None) every column it cannot prove it parses as the host does;
+``prefix_span`` stays the CPU path, the fallback and the oracle.
 """
 from __future__ import annotations
 
@@ -30,7 +35,8 @@ from typing import Dict, List, Sequence, Tuple
 
 from ...parallel import comm
 
-__all__ = ["fp_growth", "fp_growth_device", "patterns_dict", "association_rules", "prefix_span", "sequence_rules"]
+__all__ = ["fp_growth", "fp_growth_device", "patterns_dict", "association_rules", "prefix_span", "prefix_span_device",
+           "sequence_rules"]
 
 
 def _min_support(n: int, count: int, percent: float) -> int:
@@ -379,6 +385,156 @@ def prefix_span(sequences: Sequence[Sequence[Sequence[str]]], min_support_count:
     for part in comm.all_gather_object(out):
         patterns.update(part)
     return names, patterns, n
+
+
+def prefix_span_device(block, min_support_count: int, min_support_percent: float, max_pattern_length: int,
+                       backend=None, budget=None, stats=None):
+    """``prefix_span`` of this rank's sequence column (a packed ``StringBlock``) on the block's device with no per-row
+    Python: returns ``(item names, index 1.., (codes int32, lens int64, sups int64), N)`` -- the patterns as the
+    columns of ``ops.prefixspan.mine`` (step codes ``2 * item + s`` of 0-based items; ``ops.prefixspan.decode`` gives
+    the dict of ``prefix_span``) -- or None when the column cannot be proved from its bytes, on any rank, to parse as
+    the host path parses it: the caller then takes the host path.
+
+    The host parse is the contract: a row that is NULL or strips to nothing is an empty sequence that still counts in
+    N; any other row is ``s.split(";")``, every element ``.strip()``ped and ``.split(",")``.  Here a row is empty
+    when it is NULL or every byte is ASCII whitespace (0x09-0x0d, 0x1c-0x20); elements are trimmed of those bytes and
+    split on the comma.  None is returned for a column with an empty item after the trim (a doubled, leading or
+    trailing delimiter in a non-empty row: Python's ``split`` keeps an empty-string item there), an element whose
+    first or last character has the UTF-8 lead byte C2, E1, E2 or E3 (it could be Unicode whitespace that ``strip()``
+    removes), a row of more than 64 elements (judged on the raw count), or a hash collision in ``unique_ids``.
+
+    Items qualify by occurrences over all ranks and are ordered by ``(-count, name)`` as in ``prefix_span``; only the
+    distinct items with their counts cross ranks (one ``all_gather_object``), then each level's integer counts.
+    ``backend`` is an ``ops.prefixspan.Backend`` (default: the kernels on a GPU block, the torch twins on a CPU
+    block); ``stats`` (a list) receives the encode stage's time and then one entry per level."""
+    import time
+    import torch
+    from ...common.strings import StringBlock
+    from ...ops import prefixspan as S
+    from ...ops.strings import split_tokens, unique_ids
+    dev = block.device
+    t0 = time.perf_counter()
+    if backend is None:
+        backend = S.DEVICE if dev.type == "cuda" else S.TWIN
+    n_local = len(block)
+    d, off = block.data, block.offsets.to(torch.int64)
+    nb = int(d.numel())
+
+    def _ws(x):
+        return ((x >= 0x09) & (x <= 0x0d)) | ((x >= 0x1c) & (x <= 0x20))
+
+    def _trimmed(blk):
+        """First and last byte positions of every string of ``blk`` that are not ASCII whitespace (last < first:
+        there is none)."""
+        k = len(blk)
+        lens = blk.lengths()
+        seg = torch.repeat_interleave(torch.arange(k, device=dev), lens, output_size=int(blk.data.numel()))
+        solid = torch.nonzero(~_ws(blk.data)).reshape(-1)
+        first = torch.full((k,), int(blk.data.numel()), dtype=torch.int64, device=dev)
+        last = torch.full((k,), -1, dtype=torch.int64, device=dev)
+        first.scatter_reduce_(0, seg[solid], solid, reduce="amin")
+        last.scatter_reduce_(0, seg[solid], solid, reduce="amax")
+        return first, last
+
+    cum = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
+    if nb:
+        torch.cumsum((~_ws(d)).to(torch.int64), 0, out=cum[1:])
+    empty = (cum[off[1:]] - cum[off[:-1]]) == 0
+    if block.nulls is not None:
+        empty |= block.nulls.to(dev)
+    live_rows = ~empty
+    names_local: List[str] = []
+    counts_local: List[int] = []
+    undecided = False
+    ids = el_row = el_of_tok = None
+    u = 0
+    if bool(live_rows.any()):
+        # a trailing ';' ends a row with an empty element, which split_tokens would drop
+        undecided = bool((d[(off[1:] - 1)[live_rows]] == ord(";")).any())
+        if not undecided:
+            els, el_row = split_tokens(block, ord(";"))
+            keep = live_rows[el_row]
+            els, el_row = els.take(torch.nonzero(keep).reshape(-1)), el_row[keep]
+            undecided = int(torch.bincount(el_row, minlength=1).max()) > 64
+        if not undecided:
+            ed = els.data
+            first, last = _trimmed(els)
+            undecided = bool((last < first).any())                          # an element of whitespace only
+        if not undecided:
+            comma = ed == ord(",")
+            b0, b1 = ed[first], ed[last]
+            risky = (b0 == 0xC2) | ((b0 >= 0xE1) & (b0 <= 0xE3))
+            # the lead byte of the last character: one back for a 2-byte character, two back for a 3-byte one
+            cont = (b1 >= 0x80) & (b1 < 0xC0)
+            p1, p2 = ed[(last - 1).clamp(min=0)], ed[(last - 2).clamp(min=0)]
+            risky |= cont & (last - 1 >= first) & (p1 == 0xC2)
+            risky |= cont & (last - 2 >= first) & (p2 >= 0xE1) & (p2 <= 0xE3)
+            undecided = bool(risky.any() or comma[first].any() or comma[last].any()
+                             or (comma[1:] & comma[:-1]).any())
+        if not undecided:
+            ln = last - first + 1
+            toff = torch.zeros(int(ln.numel()) + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(ln, 0, out=toff[1:])
+            src = torch.repeat_interleave(first - toff[:-1], ln) + torch.arange(int(toff[-1]), device=dev)
+            tok, el_of_tok = split_tokens(StringBlock(ed[src], toff), ord(","))
+            enc = unique_ids(tok)
+            if enc is None:
+                undecided = True
+            else:
+                ids, rep = enc
+                u = int(rep.numel())
+                counts_local = torch.bincount(ids, minlength=u).cpu().tolist()     # occurrences, duplicates included
+                names_local = tok.take(rep).to_list()
+    counts = Counter()
+    n = 0
+    gathered = comm.all_gather_object((undecided, names_local, counts_local, n_local))
+    if any(g[0] for g in gathered):
+        return None
+    for _, nm, ct, nl in gathered:
+        for k, c in zip(nm, ct):
+            counts[k] += c
+        n += nl
+    min_sup = _min_support(n, min_support_count, min_support_percent)
+    qualified = [(it, c) for it, c in counts.items() if c >= min_sup]
+    qualified.sort(key=lambda t: (-t[1], t[0]))
+    names = [None] + [it for it, _ in qualified]
+    index = {it: i for i, (it, _) in enumerate(qualified)}
+    m = len(qualified)
+    w = 8
+    crow = torch.zeros(n_local * w + 1, dtype=torch.int64, device=dev)
+    item = torch.zeros(0, dtype=torch.int32, device=dev)
+    item_sup = torch.zeros(m, dtype=torch.int64, device=dev)
+    if m and u:
+        lut = torch.tensor([index.get(s, -1) for s in names_local], dtype=torch.int64, device=dev)
+        r = lut[ids]
+        ok = r >= 0
+        # distinct (element, rank), by element then rank; elements left empty drop out and the rest close up
+        n_el = int(el_row.numel())
+        key = torch.unique(el_of_tok[ok] * m + r[ok])
+        el = torch.div(key, m, rounding_mode="floor")
+        r = key - el * m
+        has = torch.zeros(n_el, dtype=torch.bool, device=dev)
+        has[el] = True
+        seq_len = torch.bincount(el_row[has], minlength=n_local)
+        before = torch.cumsum(has.to(torch.int64), 0) - has.to(torch.int64)
+        row_first = torch.cumsum(seq_len, 0) - seq_len
+        j = before[el] - row_first[el_row[el]]                  # the element's place among its row's kept elements
+        w = S.field_width(int(seq_len.max()))
+        slot = el_row[el] * w + j
+        crow = torch.zeros(n_local * w + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(torch.bincount(slot, minlength=n_local * w), 0, out=crow[1:])
+        item = r.to(torch.int32)
+        item_sup = torch.bincount(torch.unique(el_row[el] * m + r) % m, minlength=m)
+    if m:
+        comm.all_reduce(item_sup, "sum")                        # level 1: distinct (sequence, item) pairs
+    if stats is not None:
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        stats.append({"stage": "encode", "seconds": time.perf_counter() - t0, "rows": n_local, "items": m,
+                      "entries": int(item.numel()), "w": w})
+    cols = S.mine(crow, item, m, n_local, w, item_sup, min_sup, int(max_pattern_length), backend, budget=budget,
+                  stats=stats)
+    return names, cols, n
 
 
 def sequence_rules(patterns, n: int, min_confidence: float):

@@ -117,18 +117,45 @@ def _encode_seq(names, elements) -> str:
     return ELEMENT_SEP.join(ITEM_SEP.join(names[i] for i in el) for el in elements)
 
 
+def _prefixspan_device_patterns(mt, p, device, backend=None):
+    """``(names, patterns dict, N)`` as ``M.prefix_span`` gives them, through ``M.prefix_span_device`` on ``device``,
+    or None when the rows send the operator down the host path."""
+    from ...models.nlp.text import _string_block
+    from ...ops import prefixspan as SPM
+    res = M.prefix_span_device(_string_block(mt, p.get("itemsCol"), device), int(p.get("minSupportCount")),
+                               float(p.get("minSupportPercent")), int(p.get("maxPatternLength")), backend=backend)
+    if res is None:
+        return None
+    names, cols, n = res
+    return names, SPM.decode(cols), n
+
+
 class PrefixSpanBatchOp(BatchOperator):
+    """Sequential patterns (output) and sequence rules (side output 0).  On a GPU the patterns are mined by
+    ``M.prefix_span_device`` (``ops.prefixspan.device_selected``; ``ALINK_PREFIXSPAN_HIP=0`` turns it off); the host
+    path is the CPU path and the fallback for columns the device path declines.  Rows, order and strings are built
+    from the pattern dict by the same code on both paths."""
+
     def linkFrom(self, *inputs):
         mt = self.checkAndGetFirst(inputs).getOutputTable()
         p = self.resolvedParams()
-        seqs = []
-        for s in mt.col(p.get("itemsCol")).to_list():
-            if s is None or not s.strip():
-                seqs.append([])
-                continue
-            seqs.append([el.strip().split(ITEM_SEP) for el in s.split(ELEMENT_SEP)])
-        names, pats, n = M.prefix_span(seqs, int(p.get("minSupportCount")), float(p.get("minSupportPercent")),
-                                       int(p.get("maxPatternLength")))
+        from ...ops import prefixspan as SPM
+        n_rows = mt.num_rows
+        if comm.get_world_size() > 1 and torch.device(self.env.device).type == "cuda":
+            n_rows = sum(comm.all_gather_object(n_rows))        # every rank takes the same path
+        res = None
+        if SPM.device_selected(self.env.device, n_rows):
+            res = _prefixspan_device_patterns(mt, p, self.env.device)
+        if res is None:                 # not selected, or a column the device path declines
+            seqs = []
+            for s in mt.col(p.get("itemsCol")).to_list():
+                if s is None or not s.strip():
+                    seqs.append([])
+                    continue
+                seqs.append([el.strip().split(ITEM_SEP) for el in s.split(ELEMENT_SEP)])
+            res = M.prefix_span(seqs, int(p.get("minSupportCount")), float(p.get("minSupportPercent")),
+                                int(p.get("maxPatternLength")))
+        names, pats, n = res
         order = sorted(pats, key=lambda t: (sum(len(e) for e in t), t))
         prow = [(_encode_seq(names, pat), int(pats[pat]), sum(len(e) for e in pat)) for pat in order]
         rules = M.sequence_rules(pats, n, float(p.get("minConfidence")))

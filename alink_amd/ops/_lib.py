@@ -200,6 +200,8 @@ _SIGNATURES = {
     "alink_fpm_pair_counts": [_c_vp, _c_int, _c_i64, _c_vp, _c_int, _c_int, _c_vp],
     "alink_fpm_class_counts": [_c_vp, _c_i64, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_int,
                                _c_vp],
+    "alink_fpm_seq_counts": [_c_vp, _c_i64, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_vp, _c_int, _c_i64, _c_int,
+                             _c_vp],
     "alink_ar_alloc": [_c_i64, ctypes.POINTER(_c_vp)],
     "alink_ar_free": [_c_vp],
     "alink_ar_ipc_handle": [_c_vp, _c_vp],

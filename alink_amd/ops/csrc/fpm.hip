@@ -24,6 +24,16 @@
 //   popcounts into that extension's per-lane counter.  The counters stay in registers across the steps of the
 //   range; a butterfly adds the lanes and lane 0 adds once per (candidate, unit).  With ``skip`` a step whose
 //   prefix AND is zero in every lane goes without its extension loads.
+// * alink_fpm_seq_counts — sequential patterns (``ops/prefixspan.py``) on a bitmap with one field of w bits (8, 16,
+//   32 or 64) per sequence, 64 / w sequences per word: bit j of sequence t's field in row i says that element j of
+//   the sequence holds item i.  A pattern is a row of step codes 2 * item + s (s = 1: the item opens a new element,
+//   s = 0: it joins the last one); its bitmap holds bit j of a field when a match ends at element j:
+//   ``cur = B[item_0]``, S-step ``cur = after(cur) & B[i]``, I-step ``cur &= B[i]``, where ``after`` keeps, in every
+//   field, the bits strictly above the lowest set bit.  The support is the number of non-zero fields.  Same shape
+//   as the class kernel: a wave owns (class, range of words); per step of 128 words it runs the parent's chain of P
+//   loads in two registers per lane, forms ``after(cur)`` once, then per extension one 16-byte load, an AND with
+//   ``cur`` or ``after(cur)`` by the code's low bit and the non-zero-field count.  Instantiated on w, so the field
+//   masks are constants; no carry or shift leaves a field.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -205,6 +215,118 @@ int fpm_cus() {
     return cus;
 }
 
+// the field constants of a w-bit layout: bit 0 of every field, and the in-field positions below s
+template <int WB> struct Field {
+    static constexpr u64 L = WB == 8 ? 0x0101010101010101ull : WB == 16 ? 0x0001000100010001ull
+                             : WB == 32 ? 0x0000000100000001ull : 1ull;
+    static constexpr u64 H = L << (WB - 1);
+    static constexpr u64 low(int s) { return L * ((1ull << s) - 1ull); }
+};
+
+// in every field, the bits strictly above the lowest set bit (none when the field is zero or only its top bit is set)
+template <int WB>
+__device__ __forceinline__ u64 seq_after(u64 x) {
+    if constexpr (WB == 64) {
+        return x ? ~(x ^ (x - 1)) : 0ull;
+    } else {
+        u64 y = x;
+#pragma unroll
+        for (int s = 1; s <= WB / 2; s *= 2) y |= (y << s) & ~Field<WB>::low(s);     // smear upwards inside the field
+        return (y << 1) & ~Field<WB>::L;
+    }
+}
+
+// the number of non-zero fields: the add carries into a field's top bit when a lower bit is set, never beyond it
+template <int WB>
+__device__ __forceinline__ uint32_t seq_fields(u64 x) {
+    constexpr u64 H = Field<WB>::H;
+    return (uint32_t)__popcll((((x & ~H) + ~H) | x) & H);
+}
+
+template <int WB>
+__global__ __launch_bounds__(FPM_THREADS) void fpm_seq_kernel(
+        const u64* __restrict__ B, int64_t W, const int* __restrict__ prefix, int P,
+        const int64_t* __restrict__ cls_ptr, const int* __restrict__ ext, int64_t n_classes,
+        int64_t splits, int64_t chunk, u64* __restrict__ counts) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * (FPM_THREADS / 64) + (threadIdx.x >> 6);
+    const int64_t nwave = (int64_t)gridDim.x * (FPM_THREADS / 64);
+    const int64_t units = n_classes * splits;
+    // every quantity that steers a loop or a branch below is the same in all 64 lanes of the wave
+    for (int64_t u = wave; u < units; u += nwave) {
+        const int64_t c = u / splits;
+        const int64_t w_lo = (u - c * splits) * chunk;
+        const int64_t w_hi = w_lo + chunk < W ? w_lo + chunk : W;
+        const int64_t e_lo = cls_ptr[c], e_hi = cls_ptr[c + 1];
+        const int* __restrict__ pre = prefix + c * P;
+        for (int64_t e0 = e_lo; e0 < e_hi; e0 += FPM_ET) {
+            const int ne = e_hi - e0 < FPM_ET ? (int)(e_hi - e0) : FPM_ET;
+            uint32_t cnt[FPM_ET];
+            const u64* rows[FPM_ET];
+            bool sstep[FPM_ET];
+#pragma unroll
+            for (int e = 0; e < FPM_ET; ++e) {
+                const int code = ext[e0 + (e < ne ? e : 0)];
+                cnt[e] = 0;
+                rows[e] = B + (int64_t)(code >> 1) * W;
+                sstep[e] = code & 1;
+            }
+            for (int64_t w0 = w_lo; w0 < w_hi; w0 += FPM_STEP) {
+                const int64_t w = w0 + 2 * lane;            // even, and W is even: w < w_hi covers w + 1
+                const bool in = w < w_hi;
+                u64x2 cur = {0, 0};
+                if (in) {
+                    cur = *reinterpret_cast<const u64x2*>(B + (int64_t)(pre[0] >> 1) * W + w);
+                    for (int q = 1; q < P; ++q) {
+                        const int code = pre[q];
+                        const u64x2 v = *reinterpret_cast<const u64x2*>(B + (int64_t)(code >> 1) * W + w);
+                        if (code & 1) {
+                            cur.x = seq_after<WB>(cur.x);
+                            cur.y = seq_after<WB>(cur.y);
+                        }
+                        cur.x &= v.x;
+                        cur.y &= v.y;
+                    }
+                }
+                const u64x2 aft = {seq_after<WB>(cur.x), seq_after<WB>(cur.y)};
+#pragma unroll
+                for (int e = 0; e < FPM_ET; ++e) {
+                    if (e < ne && in) {
+                        const u64x2 v = *reinterpret_cast<const u64x2*>(rows[e] + w);
+                        const u64x2 p = sstep[e] ? aft : cur;
+                        cnt[e] += seq_fields<WB>(v.x & p.x) + seq_fields<WB>(v.y & p.y);
+                    }
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < FPM_ET; ++e) {
+                if (e < ne) {
+                    const uint32_t s = wave_sum(cnt[e]);
+                    if (lane == 0 && s) atomicAdd(counts + e0 + e, (u64)s);
+                }
+            }
+        }
+    }
+}
+
+// the grid, the words per unit (a multiple of 128) and the units per class of the two class-shaped kernels
+void class_shape(int64_t W, int64_t n_classes, int grid, int64_t& chunk, int64_t& g, int64_t& splits) {
+    g = grid > 0 ? grid : (int64_t)fpm_cus() * 16;
+    const int64_t waves = g * (FPM_THREADS / 64);
+    const int64_t steps = (W + FPM_STEP - 1) / FPM_STEP;
+    if (chunk == 0) {
+        int64_t s = (4 * waves + n_classes - 1) / n_classes;
+        const int64_t most = (steps + 3) / 4;               // at least four steps per unit
+        if (s > most) s = most;
+        if (s < 1) s = 1;
+        chunk = (steps + s - 1) / s * FPM_STEP;
+    } else {
+        chunk = (chunk + FPM_STEP - 1) / FPM_STEP * FPM_STEP;
+    }
+    splits = (W + chunk - 1) / chunk;
+    if (grid <= 0 && n_classes * splits < waves) g = (n_classes * splits + 3) / 4;
+}
+
 }  // namespace
 
 extern "C" {
@@ -259,22 +381,31 @@ int alink_fpm_class_counts(const void* B, int64_t W, const int* prefix, int P, c
                            hipStream_t stream) {
     if (W < 2 || (W & 1) || P < 1 || n_classes < 0 || chunk < 0) return 1;
     if (n_classes == 0) return 0;
-    int64_t g = grid > 0 ? grid : (int64_t)fpm_cus() * 16;
-    const int64_t waves = g * (FPM_THREADS / 64);
-    const int64_t steps = (W + FPM_STEP - 1) / FPM_STEP;
-    if (chunk == 0) {
-        int64_t s = (4 * waves + n_classes - 1) / n_classes;
-        const int64_t most = (steps + 3) / 4;               // at least four steps per unit
-        if (s > most) s = most;
-        if (s < 1) s = 1;
-        chunk = (steps + s - 1) / s * FPM_STEP;
-    } else {
-        chunk = (chunk + FPM_STEP - 1) / FPM_STEP * FPM_STEP;
-    }
-    const int64_t splits = (W + chunk - 1) / chunk;
-    if (grid <= 0 && n_classes * splits < waves) g = (n_classes * splits + 3) / 4;
+    int64_t g, splits;
+    class_shape(W, n_classes, grid, chunk, g, splits);
     hipLaunchKernelGGL(fpm_class_kernel, dim3((unsigned)g), dim3(FPM_THREADS), 0, stream, (const u64*)B, W, prefix, P,
                        cls_ptr, ext_item, n_classes, splits, chunk, skip, (u64*)counts);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// counts int64 [candidates] must be zero on entry.  ``prefix`` and ``ext`` hold step codes 2 * item + s whose items
+// lie in the rows of B (the wrapper checks); ``wbits``: bits per sequence field, 8, 16, 32 or 64.  ``chunk`` and
+// ``grid`` as in alink_fpm_class_counts.
+int alink_fpm_seq_counts(const void* B, int64_t W, const int* prefix, int P, const int64_t* cls_ptr, const int* ext,
+                         int64_t n_classes, void* counts, int wbits, int64_t chunk, int grid, hipStream_t stream) {
+    if (W < 2 || (W & 1) || P < 1 || n_classes < 0 || chunk < 0) return 1;
+    if (wbits != 8 && wbits != 16 && wbits != 32 && wbits != 64) return 1;
+    if (n_classes == 0) return 0;
+    int64_t g, splits;
+    class_shape(W, n_classes, grid, chunk, g, splits);
+#define FPM_SEQ_LAUNCH(WB)                                                                                          \
+    hipLaunchKernelGGL(fpm_seq_kernel<WB>, dim3((unsigned)g), dim3(FPM_THREADS), 0, stream, (const u64*)B, W, prefix, \
+                       P, cls_ptr, ext, n_classes, splits, chunk, (u64*)counts)
+    if (wbits == 8) FPM_SEQ_LAUNCH(8);
+    else if (wbits == 16) FPM_SEQ_LAUNCH(16);
+    else if (wbits == 32) FPM_SEQ_LAUNCH(32);
+    else FPM_SEQ_LAUNCH(64);
+#undef FPM_SEQ_LAUNCH
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
