@@ -214,11 +214,41 @@ def _chi_rows(results):
     return [(r.colName, gson_dumps(r)) for r in results]
 
 
+def _chisq_device_results(mt, cols, vector_col, label_col, device):
+    """The tests' results from the device path (``models/statistics/chisq``) when ``ops.chisq.device_selected``
+    says so and every column can be coded exactly; None: the operator runs its host path."""
+    import torch
+    if device is None or torch.device(device).type != "cuda":
+        return None
+    from ...models.statistics import chisq as CQ
+    from ...ops import chisq as Q
+    vecs = []                       # the vector column parsed at most once, and only when the flag leaves it open
+
+    def parsed():
+        if not vecs:
+            vecs.append(CQ.parse_vectors(mt, vector_col) if vector_col else None)
+        return vecs[0]
+
+    if not Q.device_selected(device, lambda: CQ.global_cells(mt, cols, vector_col, parsed())):
+        return None
+    got = CQ.chi_square_arrays(mt, cols, vector_col, label_col, Q.DEVICE, device, vecs=parsed())
+    if got is None:
+        return None
+    names, value, df, pv = got
+    return [ST.ChiSquareTestResult(df[j], pv[j], value[j], col=names[j]) for j in range(len(names))]
+
+
 class ChiSquareTestBatchOp(BatchOperator):
+    _device_results = None          # the results when the device path ran: the selectors read p from them
+
     def linkFrom(self, *inputs):
         mt = self.checkAndGetFirst(inputs).getOutputTable()
         p = self.getParams()
         cols = list(p.get("selectedCols"))
+        self._device_results = _chisq_device_results(mt, cols, None, p.get("labelCol"), self.env.device)
+        if self._device_results is not None:
+            self.setOutputTable(MTable.from_rows(_chi_rows(self._device_results), _CHI_SCHEMA, replicated=True))
+            return self
         label = mt.column_values(p.get("labelCol"))
         pairs = []
         for c in cols:
@@ -244,6 +274,11 @@ class VectorChiSquareTestBatchOp(ChiSquareTestBatchOp):
         from ...common.linalg import SparseVector, VectorUtil
         mt = self.checkAndGetFirst(inputs).getOutputTable()
         p = self.getParams()
+        self._device_results = _chisq_device_results(mt, None, p.get("selectedCol"), p.get("labelCol"),
+                                                     self.env.device)
+        if self._device_results is not None:
+            self.setOutputTable(MTable.from_rows(_chi_rows(self._device_results), _CHI_SCHEMA, replicated=True))
+            return self
         label = mt.column_values(p.get("labelCol"))
         vecs = [VectorUtil.getVector(v) if v is not None else None for v in mt.column_values(p.get("selectedCol"))]
         d = max([v.size() for v in vecs if v is not None] + [0])
@@ -310,6 +345,19 @@ def _chisq_select(results, p: Params):
     return sel
 
 
+def _chisq_test_results(test):
+    """The results of a linked test operator for ``_chisq_select``: the arrays of the device path when it ran, else
+    the operator's rows read back, as before."""
+    import json as _json
+    if test._device_results is not None:
+        return test._device_results
+    out = []
+    for r in test.collect():
+        d = _json.loads(r[1])
+        out.append(ST.ChiSquareTestResult(d["df"], d["p"], d["value"], col=r[0]))
+    return out
+
+
 class ChiSqSelectorBatchOp(BatchOperator):
     """Chi-square feature selection over ``selectedCols`` (reference ``ChiSqSelectorBatchOp`` ->
     ``ChiSquareTestUtil.selector``); output = model table with the selected column indices (JSON int[])."""
@@ -320,8 +368,7 @@ class ChiSqSelectorBatchOp(BatchOperator):
         p = self.getParams()
         test = ChiSquareTestBatchOp(p.clone()).linkFrom(inp)
         import json as _json
-        res = [ST.ChiSquareTestResult(_json.loads(r[1])["df"], _json.loads(r[1])["p"], _json.loads(r[1])["value"],
-                                      col=r[0]) for r in test.collect()]
+        res = _chisq_test_results(test)
         sel = _chisq_select(res, p)
         rows = SimpleModelDataConverter.rows_from(Params(), [_json.dumps(sel, separators=(",", ":"))])
         self.setOutputTable(MTable.from_rows(rows, SimpleModelDataConverter().getModelSchema(), replicated=True))
@@ -345,8 +392,7 @@ class VectorChiSqSelectorBatchOp(ChiSqSelectorBatchOp):
         inp = self.checkAndGetFirst(inputs)
         p = self.getParams()
         test = VectorChiSquareTestBatchOp(p.clone()).linkFrom(inp)
-        res = [ST.ChiSquareTestResult(_json.loads(r[1])["df"], _json.loads(r[1])["p"], _json.loads(r[1])["value"],
-                                      col=r[0]) for r in test.collect()]
+        res = _chisq_test_results(test)
         sel = _chisq_select(res, p)
         rows = SimpleModelDataConverter.rows_from(Params(), [_json.dumps(sel, separators=(",", ":"))])
         self.setOutputTable(MTable.from_rows(rows, SimpleModelDataConverter().getModelSchema(), replicated=True))

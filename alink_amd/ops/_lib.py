@@ -202,6 +202,9 @@ _SIGNATURES = {
                                _c_vp],
     "alink_fpm_seq_counts": [_c_vp, _c_i64, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_vp, _c_int, _c_i64, _c_int,
                              _c_vp],
+    "alink_chisq_counts": [_c_vp, _c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_i64, _c_int, _c_int, _c_vp],
+    "alink_chisq_stat": [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp,
+                         _c_vp, _c_int, _c_vp],
     "alink_ar_alloc": [_c_i64, ctypes.POINTER(_c_vp)],
     "alink_ar_free": [_c_vp],
     "alink_ar_ipc_handle": [_c_vp, _c_vp],
