@@ -44,6 +44,40 @@ def _min_support(n: int, count: int, percent: float) -> int:
 
 
 # ---------------------------------------------------------------------------------------------------
+# shared by the two device paths
+# ---------------------------------------------------------------------------------------------------
+def _ascii_ws(d):
+    """The bytes of ``d`` that are ASCII whitespace to Python's ``strip()``: 0x09-0x0d and 0x1c-0x20."""
+    return ((d >= 0x09) & (d <= 0x0d)) | ((d >= 0x1c) & (d <= 0x20))
+
+
+def _vote_items(undecided: bool, names_local, counts_local, n_local: int, min_support_count, min_support_percent):
+    """The one ``all_gather_object`` of a device path: every rank's verdict, distinct items with their counts, and
+    row count.  None when any rank is undecided; else ``(qualified, n, min_sup)``: the ``(item, count)`` over all
+    ranks that reach the minimum support, by ``(-count, name)``, the rows of all ranks and the minimum support."""
+    gathered = comm.all_gather_object((undecided, names_local, counts_local, n_local))
+    if any(g[0] for g in gathered):
+        return None
+    counts = Counter()
+    n = 0
+    for _, nm, ct, nl in gathered:
+        for k, c in zip(nm, ct):
+            counts[k] += c
+        n += nl
+    min_sup = _min_support(n, min_support_count, min_support_percent)
+    qualified = [(it, c) for it, c in counts.items() if c >= min_sup]
+    qualified.sort(key=lambda t: (-t[1], t[0]))
+    return qualified, n, min_sup
+
+
+def _rank_lut(qualified, names_local, dev):
+    """int64 [local ids]: the 0-based place of every local item among ``qualified``, -1 when it did not qualify."""
+    import torch
+    index = {it: i for i, (it, _) in enumerate(qualified)}
+    return torch.tensor([index.get(s, -1) for s in names_local], dtype=torch.int64, device=dev)
+
+
+# ---------------------------------------------------------------------------------------------------
 # FP-Growth
 # ---------------------------------------------------------------------------------------------------
 def _mine(db: List[Tuple[Tuple[int, ...], int]], suffix: Tuple[int, ...], min_sup: int, max_len: int,
@@ -139,7 +173,7 @@ def fp_growth_device(block, min_support_count: int, min_support_percent: float, 
     n_local = len(block)
     d, off = block.data, block.offsets.to(torch.int64)
     nb = int(d.numel())
-    ws = ((d >= 0x09) & (d <= 0x0d)) | ((d >= 0x1c) & (d <= 0x20))
+    ws = _ascii_ws(d)
     high = d >= 0x80
 
     def _per_row(mask):
@@ -171,26 +205,17 @@ def fp_growth_device(block, min_support_count: int, min_support_percent: float, 
                 pair = torch.unique(doc * u + ids)                  # distinct (row, item), by row then item id
                 counts_local = torch.bincount(pair % u, minlength=u).cpu().tolist()
                 names_local = tok.take(rep).to_list()
-    counts = Counter()
-    n = 0
-    gathered = comm.all_gather_object((undecided, names_local, counts_local, n_local))
-    if any(g[0] for g in gathered):
+    vote = _vote_items(undecided, names_local, counts_local, n_local, min_support_count, min_support_percent)
+    if vote is None:
         return None
-    for _, nm, ct, nl in gathered:
-        counts.update(dict(zip(nm, ct)))
-        n += nl
-    min_sup = _min_support(n, min_support_count, min_support_percent)
-    qualified = [(it, c) for it, c in counts.items() if c >= min_sup]
-    qualified.sort(key=lambda t: (-t[1], t[0]))
+    qualified, n, min_sup = vote
     names = [it for it, _ in qualified]
-    index = {it: i for i, it in enumerate(names)}
     m = len(names)
-    sup_by_index = {index[it]: c for it, c in qualified}
+    sup_by_index = {i: c for i, (_, c) in enumerate(qualified)}
     crow = torch.zeros(n_local + 1, dtype=torch.int64, device=dev)
     item = torch.zeros(0, dtype=torch.int32, device=dev)
     if m and pair is not None and pair.numel():
-        lut = torch.tensor([index.get(s, -1) for s in names_local], dtype=torch.int64, device=dev)
-        row, r = torch.div(pair, u, rounding_mode="floor"), lut[pair % u]
+        row, r = torch.div(pair, u, rounding_mode="floor"), _rank_lut(qualified, names_local, dev)[pair % u]
         ok = r >= 0
         key = torch.sort(row[ok] * m + r[ok]).values                # by row, then by rank: ascending within a row
         row = torch.div(key, m, rounding_mode="floor")
@@ -420,16 +445,13 @@ def prefix_span_device(block, min_support_count: int, min_support_percent: float
     d, off = block.data, block.offsets.to(torch.int64)
     nb = int(d.numel())
 
-    def _ws(x):
-        return ((x >= 0x09) & (x <= 0x0d)) | ((x >= 0x1c) & (x <= 0x20))
-
     def _trimmed(blk):
         """First and last byte positions of every string of ``blk`` that are not ASCII whitespace (last < first:
         there is none)."""
         k = len(blk)
         lens = blk.lengths()
         seg = torch.repeat_interleave(torch.arange(k, device=dev), lens, output_size=int(blk.data.numel()))
-        solid = torch.nonzero(~_ws(blk.data)).reshape(-1)
+        solid = torch.nonzero(~_ascii_ws(blk.data)).reshape(-1)
         first = torch.full((k,), int(blk.data.numel()), dtype=torch.int64, device=dev)
         last = torch.full((k,), -1, dtype=torch.int64, device=dev)
         first.scatter_reduce_(0, seg[solid], solid, reduce="amin")
@@ -438,7 +460,7 @@ def prefix_span_device(block, min_support_count: int, min_support_percent: float
 
     cum = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
     if nb:
-        torch.cumsum((~_ws(d)).to(torch.int64), 0, out=cum[1:])
+        torch.cumsum((~_ascii_ws(d)).to(torch.int64), 0, out=cum[1:])
     empty = (cum[off[1:]] - cum[off[:-1]]) == 0
     if block.nulls is not None:
         empty |= block.nulls.to(dev)
@@ -485,28 +507,18 @@ def prefix_span_device(block, min_support_count: int, min_support_percent: float
                 u = int(rep.numel())
                 counts_local = torch.bincount(ids, minlength=u).cpu().tolist()     # occurrences, duplicates included
                 names_local = tok.take(rep).to_list()
-    counts = Counter()
-    n = 0
-    gathered = comm.all_gather_object((undecided, names_local, counts_local, n_local))
-    if any(g[0] for g in gathered):
+    vote = _vote_items(undecided, names_local, counts_local, n_local, min_support_count, min_support_percent)
+    if vote is None:
         return None
-    for _, nm, ct, nl in gathered:
-        for k, c in zip(nm, ct):
-            counts[k] += c
-        n += nl
-    min_sup = _min_support(n, min_support_count, min_support_percent)
-    qualified = [(it, c) for it, c in counts.items() if c >= min_sup]
-    qualified.sort(key=lambda t: (-t[1], t[0]))
+    qualified, n, min_sup = vote
     names = [None] + [it for it, _ in qualified]
-    index = {it: i for i, (it, _) in enumerate(qualified)}
     m = len(qualified)
     w = 8
     crow = torch.zeros(n_local * w + 1, dtype=torch.int64, device=dev)
     item = torch.zeros(0, dtype=torch.int32, device=dev)
     item_sup = torch.zeros(m, dtype=torch.int64, device=dev)
     if m and u:
-        lut = torch.tensor([index.get(s, -1) for s in names_local], dtype=torch.int64, device=dev)
-        r = lut[ids]
+        r = _rank_lut(qualified, names_local, dev)[ids]
         ok = r >= 0
         # distinct (element, rank), by element then rank; elements left empty drop out and the rest close up
         n_el = int(el_row.numel())

@@ -15,7 +15,7 @@ from typing import Optional
 
 import torch  # noqa: F401  (loads torch's HIP runtime first; our .so resolves libamdhip64.so.7 to it)
 
-__all__ = ["lib", "require", "available", "kernels_enabled", "call", "query", "LIB_PATH", "stream_ptr"]
+__all__ = ["lib", "require", "available", "kernels_enabled", "sized_gate", "call", "query", "LIB_PATH", "stream_ptr"]
 
 LIB_PATH = os.environ.get("ALINK_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libalink_hip.so")
 _lib: Optional[ctypes.CDLL] = None
@@ -198,8 +198,7 @@ _SIGNATURES = {
                                _c_vp, _c_int, _c_vp],
     "alink_fpm_bitmap": [_c_vp, _c_vp, _c_i64, _c_int, _c_i64, _c_vp, _c_vp, _c_int, _c_vp],
     "alink_fpm_pair_counts": [_c_vp, _c_int, _c_i64, _c_vp, _c_int, _c_int, _c_vp],
-    "alink_fpm_class_counts": [_c_vp, _c_i64, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_int,
-                               _c_vp],
+    "alink_fpm_class_counts": [_c_vp, _c_i64, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_vp],
     "alink_fpm_seq_counts": [_c_vp, _c_i64, _c_vp, _c_int, _c_vp, _c_vp, _c_i64, _c_vp, _c_int, _c_i64, _c_int,
                              _c_vp],
     "alink_chisq_counts": [_c_vp, _c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_i64, _c_int, _c_int, _c_vp],
@@ -260,6 +259,18 @@ def kernels_enabled() -> bool:
         return False
     require()       # raises: no quiet fall-back on a GPU
     return True
+
+
+def sized_gate(flag: str, device, size, minimum: int) -> bool:
+    """The gate of an operator whose device path pays off from a size on: False off a CUDA device or with the
+    environment flag ``flag`` at ``0``; below ``minimum`` False too unless the flag is ``1``; else ``kernels_enabled()``.
+    ``size`` is a number or a function that gives it, called only when the size decides."""
+    value = os.environ.get(flag, "")
+    if torch.device(device).type != "cuda" or value == "0":
+        return False
+    if value != "1" and int(size() if callable(size) else size) < minimum:
+        return False
+    return kernels_enabled()
 
 
 def stream_ptr(device=None) -> int:

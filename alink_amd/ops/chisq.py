@@ -20,7 +20,6 @@ any size) and ``_lib.kernels_enabled()`` (no quiet fall-back).
 """
 from __future__ import annotations
 
-import os
 from typing import Callable, List, NamedTuple, Optional, Tuple
 
 import torch
@@ -52,12 +51,7 @@ def device_selected(device, cells) -> bool:
     ``ALINK_CHISQ_HIP=0``, ``cells >= CHISQ_MIN_CELLS`` unless ``ALINK_CHISQ_HIP=1`` forces it, and the kernel
     library by the one fall-back rule (``_lib.kernels_enabled``: a missing library is an error).  ``cells`` may be
     a function that counts them: it is called only when the size decides (counting is a collective)."""
-    flag = os.environ.get("ALINK_CHISQ_HIP", "")
-    if torch.device(device).type != "cuda" or flag == "0":
-        return False
-    if flag != "1" and int(cells() if callable(cells) else cells) < CHISQ_MIN_CELLS:
-        return False
-    return _lib.kernels_enabled()
+    return _lib.sized_gate("ALINK_CHISQ_HIP", device, cells, CHISQ_MIN_CELLS)
 
 
 def u32(C: torch.Tensor) -> torch.Tensor:

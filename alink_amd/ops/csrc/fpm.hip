@@ -17,23 +17,25 @@
 //   runs (a broadcast on the i side, 512 contiguous bytes per wave on the j side) and every word staged is used
 //   64 times.  The 16 counters of a thread hold whole pairs: no cross-lane reduction, one add per (pair,
 //   workgroup) at the end (a plain store when the workgroup owns all words).
-// * alink_fpm_class_counts — candidates grouped by prefix: prefix int32 [classes, P], cls_ptr int64 [classes + 1]
-//   and ext_item int32 [candidates] as a CSR of each class's extension items; counts int64 [candidates].  A wave
-//   owns (class, range of ``chunk`` words) and takes the class's extensions FPM_ET at a time: per step of 128
-//   words it ANDs the P prefix rows into two registers per lane, then per extension one 16-byte load, AND and two
-//   popcounts into that extension's per-lane counter.  The counters stay in registers across the steps of the
-//   range; a butterfly adds the lanes and lane 0 adds once per (candidate, unit).  With ``skip`` a step whose
-//   prefix AND is zero in every lane goes without its extension loads.
-// * alink_fpm_seq_counts — sequential patterns (``ops/prefixspan.py``) on a bitmap with one field of w bits (8, 16,
-//   32 or 64) per sequence, 64 / w sequences per word: bit j of sequence t's field in row i says that element j of
-//   the sequence holds item i.  A pattern is a row of step codes 2 * item + s (s = 1: the item opens a new element,
-//   s = 0: it joins the last one); its bitmap holds bit j of a field when a match ends at element j:
-//   ``cur = B[item_0]``, S-step ``cur = after(cur) & B[i]``, I-step ``cur &= B[i]``, where ``after`` keeps, in every
-//   field, the bits strictly above the lowest set bit.  The support is the number of non-zero fields.  Same shape
-//   as the class kernel: a wave owns (class, range of words); per step of 128 words it runs the parent's chain of P
-//   loads in two registers per lane, forms ``after(cur)`` once, then per extension one 16-byte load, an AND with
-//   ``cur`` or ``after(cur)`` by the code's low bit and the non-zero-field count.  Instantiated on w, so the field
-//   masks are constants; no carry or shift leaves a field.
+// * alink_fpm_class_counts, alink_fpm_seq_counts — the walk (``fpm_walk_kernel``).  Candidates grouped by parent:
+//   prefix int32 [classes, P], cls_ptr int64 [classes + 1] and ext int32 [candidates] as a CSR of each class's
+//   extension codes; counts int64 [candidates].  A wave owns (class, range of ``chunk`` words) and takes the class's
+//   extensions FPM_ET at a time: per step of 128 words it runs the parent's chain of P loads in two registers per
+//   lane (``cur``), then per extension one 16-byte load, an AND and the word count into that extension's per-lane
+//   counter.  The counters stay in registers across the steps of the range; a butterfly adds the lanes and lane 0
+//   adds once per (candidate, unit).  A stateless policy, resolved at compile time, says what a code means:
+//   - ``ItemsetStep`` (``ops/fpm.py``): a code is an item, every step is ``cur &= B[item]``, a word counts its set
+//     bits.
+//   - ``SeqStep<WB>`` (sequential patterns, ``ops/prefixspan.py``): B has one field of WB bits (8, 16, 32 or 64) per
+//     sequence, 64 / WB sequences per word; bit j of sequence t's field in row i says that element j of the sequence
+//     holds item i.  A code is 2 * item + s (s = 1: the item opens a new element, s = 0: it joins the last one), and
+//     a pattern's bitmap holds bit j of a field when a match ends at element j: ``cur = B[item_0]``, S-step ``cur =
+//     after(cur) & B[i]``, I-step ``cur &= B[i]``, where ``after`` keeps, in every field, the bits strictly above the
+//     lowest set bit.  ``after(cur)`` is formed once per step and an extension ANDs with it or with ``cur`` by its
+//     code's low bit; a word counts its non-zero fields.  The field masks are constants; no carry or shift leaves a
+//     field.
+//   Leaving out the extension loads of a step whose ``cur`` is zero in every lane was measured and dropped: it was no
+//   faster (``profiles/fpgrowth.txt``).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -152,62 +154,6 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
     return v;
 }
 
-__global__ __launch_bounds__(FPM_THREADS) void fpm_class_kernel(
-        const u64* __restrict__ B, int64_t W, const int* __restrict__ prefix, int P,
-        const int64_t* __restrict__ cls_ptr, const int* __restrict__ ext_item, int64_t n_classes,
-        int64_t splits, int64_t chunk, int skip, u64* __restrict__ counts) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * (FPM_THREADS / 64) + (threadIdx.x >> 6);
-    const int64_t nwave = (int64_t)gridDim.x * (FPM_THREADS / 64);
-    const int64_t units = n_classes * splits;
-    // every quantity that steers a loop or a branch below is the same in all 64 lanes of the wave
-    for (int64_t u = wave; u < units; u += nwave) {
-        const int64_t c = u / splits;
-        const int64_t w_lo = (u - c * splits) * chunk;
-        const int64_t w_hi = w_lo + chunk < W ? w_lo + chunk : W;
-        const int64_t e_lo = cls_ptr[c], e_hi = cls_ptr[c + 1];
-        const int* __restrict__ pre = prefix + c * P;
-        for (int64_t e0 = e_lo; e0 < e_hi; e0 += FPM_ET) {
-            const int ne = e_hi - e0 < FPM_ET ? (int)(e_hi - e0) : FPM_ET;
-            uint32_t cnt[FPM_ET];
-            const u64* rows[FPM_ET];
-#pragma unroll
-            for (int e = 0; e < FPM_ET; ++e) {
-                cnt[e] = 0;
-                rows[e] = B + (int64_t)ext_item[e0 + (e < ne ? e : 0)] * W;
-            }
-            for (int64_t w0 = w_lo; w0 < w_hi; w0 += FPM_STEP) {
-                const int64_t w = w0 + 2 * lane;            // even, and W is even: w < w_hi covers w + 1
-                const bool in = w < w_hi;
-                u64x2 p = {0, 0};
-                if (in) {
-                    p = *reinterpret_cast<const u64x2*>(B + (int64_t)pre[0] * W + w);
-                    for (int q = 1; q < P; ++q) {
-                        const u64x2 v = *reinterpret_cast<const u64x2*>(B + (int64_t)pre[q] * W + w);
-                        p.x &= v.x;
-                        p.y &= v.y;
-                    }
-                }
-                if (skip && !__any((p.x | p.y) != 0)) continue;
-#pragma unroll
-                for (int e = 0; e < FPM_ET; ++e) {
-                    if (e < ne && in) {
-                        const u64x2 v = *reinterpret_cast<const u64x2*>(rows[e] + w);
-                        cnt[e] += (uint32_t)__popcll(v.x & p.x) + (uint32_t)__popcll(v.y & p.y);
-                    }
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < FPM_ET; ++e) {
-                if (e < ne) {
-                    const uint32_t s = wave_sum(cnt[e]);
-                    if (lane == 0 && s) atomicAdd(counts + e0 + e, (u64)s);
-                }
-            }
-        }
-    }
-}
-
 int fpm_cus() {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 256;
@@ -243,8 +189,24 @@ __device__ __forceinline__ uint32_t seq_fields(u64 x) {
     return (uint32_t)__popcll((((x & ~H) + ~H) | x) & H);
 }
 
-template <int WB>
-__global__ __launch_bounds__(FPM_THREADS) void fpm_seq_kernel(
+// what a code of ``prefix`` / ``ext`` means to the walk: its row of B, whether the step first applies ``after``, and
+// how a word of the result is counted
+struct ItemsetStep {
+    static __device__ __forceinline__ int row(int code) { return code; }
+    static __device__ __forceinline__ bool shifts(int) { return false; }
+    static __device__ __forceinline__ u64 after(u64 x) { return x; }
+    static __device__ __forceinline__ uint32_t count(u64 x) { return (uint32_t)__popcll(x); }
+};
+
+template <int WB> struct SeqStep {
+    static __device__ __forceinline__ int row(int code) { return code >> 1; }
+    static __device__ __forceinline__ bool shifts(int code) { return code & 1; }
+    static __device__ __forceinline__ u64 after(u64 x) { return seq_after<WB>(x); }
+    static __device__ __forceinline__ uint32_t count(u64 x) { return seq_fields<WB>(x); }
+};
+
+template <class Step>
+__global__ __launch_bounds__(FPM_THREADS) void fpm_walk_kernel(
         const u64* __restrict__ B, int64_t W, const int* __restrict__ prefix, int P,
         const int64_t* __restrict__ cls_ptr, const int* __restrict__ ext, int64_t n_classes,
         int64_t splits, int64_t chunk, u64* __restrict__ counts) {
@@ -268,33 +230,33 @@ __global__ __launch_bounds__(FPM_THREADS) void fpm_seq_kernel(
             for (int e = 0; e < FPM_ET; ++e) {
                 const int code = ext[e0 + (e < ne ? e : 0)];
                 cnt[e] = 0;
-                rows[e] = B + (int64_t)(code >> 1) * W;
-                sstep[e] = code & 1;
+                rows[e] = B + (int64_t)Step::row(code) * W;
+                sstep[e] = Step::shifts(code);
             }
             for (int64_t w0 = w_lo; w0 < w_hi; w0 += FPM_STEP) {
                 const int64_t w = w0 + 2 * lane;            // even, and W is even: w < w_hi covers w + 1
                 const bool in = w < w_hi;
                 u64x2 cur = {0, 0};
                 if (in) {
-                    cur = *reinterpret_cast<const u64x2*>(B + (int64_t)(pre[0] >> 1) * W + w);
+                    cur = *reinterpret_cast<const u64x2*>(B + (int64_t)Step::row(pre[0]) * W + w);
                     for (int q = 1; q < P; ++q) {
                         const int code = pre[q];
-                        const u64x2 v = *reinterpret_cast<const u64x2*>(B + (int64_t)(code >> 1) * W + w);
-                        if (code & 1) {
-                            cur.x = seq_after<WB>(cur.x);
-                            cur.y = seq_after<WB>(cur.y);
+                        const u64x2 v = *reinterpret_cast<const u64x2*>(B + (int64_t)Step::row(code) * W + w);
+                        if (Step::shifts(code)) {
+                            cur.x = Step::after(cur.x);
+                            cur.y = Step::after(cur.y);
                         }
                         cur.x &= v.x;
                         cur.y &= v.y;
                     }
                 }
-                const u64x2 aft = {seq_after<WB>(cur.x), seq_after<WB>(cur.y)};
+                const u64x2 aft = {Step::after(cur.x), Step::after(cur.y)};
 #pragma unroll
                 for (int e = 0; e < FPM_ET; ++e) {
                     if (e < ne && in) {
                         const u64x2 v = *reinterpret_cast<const u64x2*>(rows[e] + w);
                         const u64x2 p = sstep[e] ? aft : cur;
-                        cnt[e] += seq_fields<WB>(v.x & p.x) + seq_fields<WB>(v.y & p.y);
+                        cnt[e] += Step::count(v.x & p.x) + Step::count(v.y & p.y);
                     }
                 }
             }
@@ -309,7 +271,7 @@ __global__ __launch_bounds__(FPM_THREADS) void fpm_seq_kernel(
     }
 }
 
-// the grid, the words per unit (a multiple of 128) and the units per class of the two class-shaped kernels
+// the grid, the words per unit (a multiple of 128) and the units per class of the walk
 void class_shape(int64_t W, int64_t n_classes, int grid, int64_t& chunk, int64_t& g, int64_t& splits) {
     g = grid > 0 ? grid : (int64_t)fpm_cus() * 16;
     const int64_t waves = g * (FPM_THREADS / 64);
@@ -325,6 +287,18 @@ void class_shape(int64_t W, int64_t n_classes, int grid, int64_t& chunk, int64_t
     }
     splits = (W + chunk - 1) / chunk;
     if (grid <= 0 && n_classes * splits < waves) g = (n_classes * splits + 3) / 4;
+}
+
+template <class Step>
+int launch_walk(const void* B, int64_t W, const int* prefix, int P, const int64_t* cls_ptr, const int* ext,
+                int64_t n_classes, void* counts, int64_t chunk, int grid, hipStream_t stream) {
+    if (W < 2 || (W & 1) || P < 1 || n_classes < 0 || chunk < 0) return 1;
+    if (n_classes == 0) return 0;
+    int64_t g, splits;
+    class_shape(W, n_classes, grid, chunk, g, splits);
+    hipLaunchKernelGGL(fpm_walk_kernel<Step>, dim3((unsigned)g), dim3(FPM_THREADS), 0, stream, (const u64*)B, W, prefix,
+                       P, cls_ptr, ext, n_classes, splits, chunk, (u64*)counts);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
 }  // namespace
@@ -377,15 +351,9 @@ int alink_fpm_pair_counts(const void* B, int m, int64_t W, void* C, int chunk, i
 // counts int64 [candidates] must be zero on entry.  Items of ``prefix`` and ``ext_item`` lie in the rows of B (the
 // wrapper checks).  ``chunk``: words per unit, rounded up to a multiple of 128 (0: enough units to fill the grid).
 int alink_fpm_class_counts(const void* B, int64_t W, const int* prefix, int P, const int64_t* cls_ptr,
-                           const int* ext_item, int64_t n_classes, void* counts, int64_t chunk, int grid, int skip,
+                           const int* ext_item, int64_t n_classes, void* counts, int64_t chunk, int grid,
                            hipStream_t stream) {
-    if (W < 2 || (W & 1) || P < 1 || n_classes < 0 || chunk < 0) return 1;
-    if (n_classes == 0) return 0;
-    int64_t g, splits;
-    class_shape(W, n_classes, grid, chunk, g, splits);
-    hipLaunchKernelGGL(fpm_class_kernel, dim3((unsigned)g), dim3(FPM_THREADS), 0, stream, (const u64*)B, W, prefix, P,
-                       cls_ptr, ext_item, n_classes, splits, chunk, skip, (u64*)counts);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
+    return launch_walk<ItemsetStep>(B, W, prefix, P, cls_ptr, ext_item, n_classes, counts, chunk, grid, stream);
 }
 
 // counts int64 [candidates] must be zero on entry.  ``prefix`` and ``ext`` hold step codes 2 * item + s whose items
@@ -393,20 +361,13 @@ int alink_fpm_class_counts(const void* B, int64_t W, const int* prefix, int P, c
 // ``grid`` as in alink_fpm_class_counts.
 int alink_fpm_seq_counts(const void* B, int64_t W, const int* prefix, int P, const int64_t* cls_ptr, const int* ext,
                          int64_t n_classes, void* counts, int wbits, int64_t chunk, int grid, hipStream_t stream) {
-    if (W < 2 || (W & 1) || P < 1 || n_classes < 0 || chunk < 0) return 1;
-    if (wbits != 8 && wbits != 16 && wbits != 32 && wbits != 64) return 1;
-    if (n_classes == 0) return 0;
-    int64_t g, splits;
-    class_shape(W, n_classes, grid, chunk, g, splits);
-#define FPM_SEQ_LAUNCH(WB)                                                                                          \
-    hipLaunchKernelGGL(fpm_seq_kernel<WB>, dim3((unsigned)g), dim3(FPM_THREADS), 0, stream, (const u64*)B, W, prefix, \
-                       P, cls_ptr, ext, n_classes, splits, chunk, (u64*)counts)
-    if (wbits == 8) FPM_SEQ_LAUNCH(8);
-    else if (wbits == 16) FPM_SEQ_LAUNCH(16);
-    else if (wbits == 32) FPM_SEQ_LAUNCH(32);
-    else FPM_SEQ_LAUNCH(64);
-#undef FPM_SEQ_LAUNCH
-    return hipGetLastError() == hipSuccess ? 0 : 2;
+    switch (wbits) {
+        case 8: return launch_walk<SeqStep<8>>(B, W, prefix, P, cls_ptr, ext, n_classes, counts, chunk, grid, stream);
+        case 16: return launch_walk<SeqStep<16>>(B, W, prefix, P, cls_ptr, ext, n_classes, counts, chunk, grid, stream);
+        case 32: return launch_walk<SeqStep<32>>(B, W, prefix, P, cls_ptr, ext, n_classes, counts, chunk, grid, stream);
+        case 64: return launch_walk<SeqStep<64>>(B, W, prefix, P, cls_ptr, ext, n_classes, counts, chunk, grid, stream);
+    }
+    return 1;
 }
 
 }  // extern "C"

@@ -11,7 +11,8 @@ Three kernels, each with a torch twin of the same arguments that runs on any dev
 ``pair_counts`` (level 2: the upper triangle of the bit Gram, a tiled product through LDS) and ``class_counts``
 (levels >= 3, and level 2 above ``FPM_PAIR_MAX_ITEMS``: candidates grouped by prefix).  ``mine`` takes the three as
 a ``Backend``, so the CPU tests drive the same level loop through the twins (``TWIN``) that the operator drives
-through the kernels (``DEVICE``).
+through the kernels (``DEVICE``).  The batch loop of a level (``count_level``), the pattern columns
+(``pattern_columns``) and the grouped-candidate check are shared with the sequence miner ``ops/prefixspan.py``.
 
 ``device_selected(device, n_rows)`` decides whether ``FpGrowthBatchOp`` takes this path: a CUDA device,
 ``ALINK_FPGROWTH_HIP`` not ``0``, at least ``FPM_MIN_ROWS`` rows (``ALINK_FPGROWTH_HIP=1`` forces it at any size) and
@@ -19,7 +20,6 @@ through the kernels (``DEVICE``).
 """
 from __future__ import annotations
 
-import os
 import time
 from typing import Callable, List, NamedTuple, Optional, Tuple
 
@@ -29,8 +29,8 @@ from ..parallel import comm
 from . import _lib
 
 __all__ = ["device_selected", "row_stride", "build_bitmap", "pair_counts", "class_counts", "build_bitmap_twin",
-           "pair_counts_twin", "class_counts_twin", "u32", "Backend", "DEVICE", "TWIN", "join_siblings", "mine",
-           "FPM_CALLS", "FPM_MIN_ROWS", "FPM_PAIR_MAX_ITEMS", "FPM_BUDGET_BYTES", "FPM_SKIP"]
+           "pair_counts_twin", "class_counts_twin", "u32", "Backend", "DEVICE", "TWIN", "join_siblings",
+           "count_level", "pattern_columns", "mine", "FPM_CALLS", "FPM_MIN_ROWS", "FPM_PAIR_MAX_ITEMS", "FPM_BUDGET_BYTES"]
 
 FPM_CALLS = 0                   # launches of the HIP mining kernels (tests read it)
 FPM_MIN_ROWS = 512              # rows (over all ranks) from which the device path is taken: the measured crossover
@@ -39,22 +39,15 @@ FPM_MIN_ROWS = 512              # rows (over all ranks) from which the device pa
 FPM_PAIR_MAX_ITEMS = 16384      # above this many frequent items level 2 goes through the class kernel: C uint32
 #                                 [m, m] stays at 1 GiB
 FPM_BUDGET_BYTES = 2 ** 31      # bytes one row block's bitmap, and one batch of candidates, may take
-FPM_SKIP = False                # class kernel: leave out the extension loads of a step whose prefix AND is zero.
-#                                 Off: it measured no faster (199.7 ms with, 202.2 ms without, level 3 of 1e7 rows;
-#                                 68.1 / 68.3 ms level 4): frequent prefixes are not sparse enough to empty 8192 rows
-_CAND_BYTES = 32                # per candidate of a batch: extension, owner, position, count and the kept rows
+_CAND_BYTES = 32                # per candidate of a batch: extension, owner, position, count and the kept rows (the
+#                                 level loops of this module and of ``ops/prefixspan.py``)
 
 
 def device_selected(device, n_rows: int) -> bool:
     """True when ``FpGrowthBatchOp`` runs on the device: a CUDA device, not switched off by ``ALINK_FPGROWTH_HIP=0``,
     ``n_rows >= FPM_MIN_ROWS`` unless ``ALINK_FPGROWTH_HIP=1`` forces it, and the kernel library by the one
     fall-back rule (``_lib.kernels_enabled``: a missing library is an error)."""
-    flag = os.environ.get("ALINK_FPGROWTH_HIP", "")
-    if torch.device(device).type != "cuda" or flag == "0":
-        return False
-    if flag != "1" and int(n_rows) < FPM_MIN_ROWS:
-        return False
-    return _lib.kernels_enabled()
+    return _lib.sized_gate("ALINK_FPGROWTH_HIP", device, n_rows, FPM_MIN_ROWS)
 
 
 def row_stride(n: int) -> int:
@@ -94,23 +87,34 @@ def _check_bitmap(B: torch.Tensor, what: str) -> Tuple[int, int]:
     return int(B.shape[0]), int(B.shape[1])
 
 
-def _check_classes(B, prefix, cls_ptr, ext_item) -> Tuple[int, int, int]:
-    m, _ = _check_bitmap(B, "class_counts")
+def _check_grouped(what: str, B, prefix, cls_ptr, ext, n_codes: int) -> Tuple[int, int, int]:
+    """The candidates of a walk, grouped by parent: ``(classes, candidates, P)``.  ``n_codes``: the codes a row of
+    ``prefix`` and ``ext`` may hold are ``[0, n_codes)``."""
     dev = B.device
     if not (prefix.dtype == torch.int32 and prefix.dim() == 2 and prefix.shape[1] >= 1 and prefix.is_contiguous()
             and cls_ptr.dtype == torch.int64 and cls_ptr.dim() == 1 and cls_ptr.is_contiguous()
-            and ext_item.dtype == torch.int32 and ext_item.dim() == 1 and ext_item.is_contiguous()
-            and prefix.device == dev and cls_ptr.device == dev and ext_item.device == dev
+            and ext.dtype == torch.int32 and ext.dim() == 1 and ext.is_contiguous()
+            and prefix.device == dev and cls_ptr.device == dev and ext.device == dev
             and int(cls_ptr.numel()) == int(prefix.shape[0]) + 1):
-        raise ValueError("class_counts: prefix int32 [classes, L - 1], cls_ptr int64 [classes + 1] and ext_item int32 "
-                         "[candidates], contiguous on the bitmap's device, are needed")
-    nc, ne = int(prefix.shape[0]), int(ext_item.numel())
+        raise ValueError(f"{what}: prefix int32 [classes, P], cls_ptr int64 [classes + 1] and ext int32 [candidates], "
+                         "contiguous on the bitmap's device, are needed")
+    nc, ne = int(prefix.shape[0]), int(ext.numel())
     if int(cls_ptr[0]) != 0 or int(cls_ptr[-1]) != ne or (nc and bool((cls_ptr[1:] < cls_ptr[:-1]).any())):
-        raise ValueError("class_counts: cls_ptr must ascend from 0 to the number of candidates")
-    for t in (prefix, ext_item):
-        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= m):
-            raise ValueError("class_counts: an item outside the bitmap's rows")
+        raise ValueError(f"{what}: cls_ptr must ascend from 0 to the number of candidates")
+    for t in (prefix, ext):
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n_codes):
+            raise ValueError(f"{what}: an item outside the bitmap's rows")
     return nc, ne, int(prefix.shape[1])
+
+
+def _check_classes(B, prefix, cls_ptr, ext_item) -> Tuple[int, int, int]:
+    m, _ = _check_bitmap(B, "class_counts")
+    return _check_grouped("class_counts", B, prefix, cls_ptr, ext_item, m)
+
+
+def _owner(cnt: torch.Tensor, total: int) -> torch.Tensor:
+    """int64 [total]: the group of every member, for groups of ``cnt`` members back to back."""
+    return torch.repeat_interleave(torch.arange(int(cnt.numel()), device=cnt.device), cnt, output_size=total)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -153,20 +157,18 @@ def pair_counts(B: torch.Tensor, chunk: int = 0, splits: int = 0) -> torch.Tenso
 
 
 def class_counts(B: torch.Tensor, prefix: torch.Tensor, cls_ptr: torch.Tensor, ext_item: torch.Tensor,
-                 chunk: int = 0, grid: int = 0, skip: Optional[bool] = None) -> torch.Tensor:
+                 chunk: int = 0, grid: int = 0) -> torch.Tensor:
     """int64 [candidates] supports of candidates grouped by prefix on a GPU: candidate ``e`` of class ``c``
     (``cls_ptr[c] <= e < cls_ptr[c + 1]``) is the itemset ``prefix[c] + (ext_item[e],)``.  ``chunk``: words a wave
-    owns per unit (rounded up to 128; 0: chosen from the shape); ``grid``: workgroups; ``skip``: leave out the
-    extension loads of an all-zero prefix step (default ``FPM_SKIP``).  None of them changes a count."""
+    owns per unit (rounded up to 128; 0: chosen from the shape); ``grid``: workgroups.  Neither changes a count."""
     nc, ne, P = _check_classes(B, prefix, cls_ptr, ext_item)
     if not B.is_cuda or int(chunk) < 0 or int(grid) < 0:
         raise ValueError("class_counts: a GPU bitmap, chunk >= 0 and grid >= 0 are needed")
     counts = torch.zeros(ne, dtype=torch.int64, device=B.device)
     if ne == 0:
         return counts
-    skip = FPM_SKIP if skip is None else bool(skip)
     _lib.call("alink_fpm_class_counts", B.data_ptr(), int(B.shape[1]), prefix.data_ptr(), P, cls_ptr.data_ptr(),
-              ext_item.data_ptr(), nc, counts.data_ptr(), int(chunk), int(grid), int(skip), _lib.stream_ptr(B.device))
+              ext_item.data_ptr(), nc, counts.data_ptr(), int(chunk), int(grid), _lib.stream_ptr(B.device))
     _ran()
     return counts
 
@@ -211,14 +213,14 @@ def pair_counts_twin(B: torch.Tensor, chunk: int = 0, splits: int = 0) -> torch.
 
 
 def class_counts_twin(B: torch.Tensor, prefix: torch.Tensor, cls_ptr: torch.Tensor, ext_item: torch.Tensor,
-                      chunk: int = 0, grid: int = 0, skip: Optional[bool] = None) -> torch.Tensor:
+                      chunk: int = 0, grid: int = 0) -> torch.Tensor:
     nc, ne, P = _check_classes(B, prefix, cls_ptr, ext_item)
     dev = B.device
     counts = torch.zeros(ne, dtype=torch.int64, device=dev)
     if ne == 0:
         return counts
     W = int(B.shape[1])
-    owner = torch.repeat_interleave(torch.arange(nc, device=dev), cls_ptr[1:] - cls_ptr[:-1], output_size=ne)
+    owner = _owner(cls_ptr[1:] - cls_ptr[:-1], ne)
     step = max(1, (2 ** 22) // W)
     for e0 in range(0, ne, step):
         o = owner[e0:e0 + step]
@@ -273,7 +275,7 @@ def expand_classes(F: torch.Tensor, cls: torch.Tensor, cnt: torch.Tensor):
     ptr = torch.zeros(nc + 1, dtype=torch.int64, device=dev)
     torch.cumsum(cnt, 0, out=ptr[1:])
     total = int(ptr[-1])
-    owner = torch.repeat_interleave(torch.arange(nc, device=dev), cnt, output_size=total)
+    owner = _owner(cnt, total)
     j = torch.arange(total, device=dev) - ptr[:-1][owner]
     ext = F[cls[owner] + 1 + j, -1].contiguous()
     return F[cls].contiguous(), ptr, ext, owner
@@ -309,6 +311,51 @@ class _Blocks:
             yield B
 
 
+def count_level(cum: torch.Tensor, expand: Callable, count: Callable, blocks, budget: int, keep: int, width: int):
+    """One level's candidates counted in batches that fit the budget: ``(rows int32 [kept, width], supports int64
+    [kept])`` of the candidates whose support over all ranks is at least ``keep``, in candidate order.
+
+    ``cum`` int64 [parents] holds the running total of the parents' candidates.  A batch is a run of whole parents ``c0 .. c1 - 1``
+    with at most ``budget // _CAND_BYTES`` candidates (a single parent is the smallest batch):
+    ``expand(c0, c1)`` gives its ``(prefix, cls_ptr, ext, owner)``, ``count(B, lo, hi, prefix, cls_ptr, ext)`` its
+    supports on the bitmap ``B`` of the rows ``lo .. hi - 1`` of ``blocks``; the block counts are added and make one
+    ``comm.all_reduce`` per batch."""
+    dev = cum.device
+    cap = max(1, int(budget) // _CAND_BYTES)
+    rowsF, rowsS = [], []
+    c0, nc, done = 0, int(cum.numel()), 0
+    while c0 < nc:
+        # the last parent that still fits the batch; a single parent is the smallest batch
+        c1 = int(torch.searchsorted(cum, torch.tensor(done + cap, device=dev), right=True))
+        c1 = min(max(c1, c0 + 1), nc)
+        prefix, ptr, ext, owner = expand(c0, c1)
+        counts = torch.zeros(int(ext.numel()), dtype=torch.int64, device=dev)
+        for (lo, hi), B in zip(blocks.bounds, blocks):
+            counts += count(B, lo, hi, prefix, ptr, ext)
+        comm.all_reduce(counts, "sum")
+        ok = counts >= keep
+        rowsF.append(torch.cat([prefix[owner[ok]], ext[ok].reshape(-1, 1)], 1))
+        rowsS.append(counts[ok])
+        done = int(cum[c1 - 1])
+        c0 = c1
+    if not rowsF:
+        return (torch.zeros((0, int(width)), dtype=torch.int32, device=dev),
+                torch.zeros(0, dtype=torch.int64, device=dev))
+    return torch.cat(rowsF), torch.cat(rowsS)
+
+
+def pattern_columns(levels, dev):
+    """``(codes int32 [sum of lens], lens int64 [P], sups int64 [P])`` of the kept ``(rows, supports)`` of every
+    level: the patterns back to back, in the levels' order."""
+    if not levels:
+        return (torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int64, device=dev),
+                torch.zeros(0, dtype=torch.int64, device=dev))
+    codes = torch.cat([f.reshape(-1) for f, _ in levels])
+    lens = torch.cat([torch.full((int(f.shape[0]),), int(f.shape[1]), dtype=torch.int64, device=dev)
+                      for f, _ in levels])
+    return codes, lens, torch.cat([s for _, s in levels])
+
+
 def mine(crow: torch.Tensor, item: torch.Tensor, m: int, item_sup: torch.Tensor, min_sup: int, max_len: int,
          backend: Backend, budget: Optional[int] = None, pair_max_items: Optional[int] = None,
          stats: Optional[list] = None):
@@ -331,25 +378,12 @@ def mine(crow: torch.Tensor, item: torch.Tensor, m: int, item_sup: torch.Tensor,
     m = int(m)
     levels: List[Tuple[torch.Tensor, torch.Tensor]] = []
 
-    def _sync():
-        if stats is not None and dev.type == "cuda":
-            torch.cuda.synchronize(dev)
-
-    def _result():
-        if not levels:
-            return (torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int64, device=dev),
-                    torch.zeros(0, dtype=torch.int64, device=dev))
-        items = torch.cat([f.reshape(-1) for f, _ in levels])
-        lens = torch.cat([torch.full((int(f.shape[0]),), int(f.shape[1]), dtype=torch.int64, device=dev)
-                          for f, _ in levels])
-        return items, lens, torch.cat([s for _, s in levels])
-
     if m < 1 or int(max_len) < 1:
-        return _result()
+        return pattern_columns(levels, dev)
     one = torch.nonzero(item_sup >= keep).reshape(-1)
     F = one.to(torch.int32).reshape(-1, 1)
     if F.shape[0] == 0:
-        return _result()
+        return pattern_columns(levels, dev)
     levels.append((F, item_sup[one].to(torch.int64)))
     blocks = _Blocks(crow, item, m, backend, budget)
     L = 1
@@ -372,31 +406,12 @@ def mine(crow: torch.Tensor, item: torch.Tensor, m: int, item_sup: torch.Tensor,
             cls, cnt = join_siblings(F)
             cum = torch.cumsum(cnt, 0)
             n_cand = int(cum[-1]) if cum.numel() else 0
-            cap = max(1, budget // _CAND_BYTES)
-            rowsF, rowsS = [], []
-            c0, nc, done = 0, int(cls.numel()), 0
-            while c0 < nc:
-                # the last class that still fits the batch; a single class is the smallest batch
-                c1 = int(torch.searchsorted(cum, torch.tensor(done + cap, device=dev), right=True))
-                c1 = min(max(c1, c0 + 1), nc)
-                prefix, ptr, ext, owner = expand_classes(F, cls[c0:c1], cnt[c0:c1])
-                counts = torch.zeros(int(ext.numel()), dtype=torch.int64, device=dev)
-                for B in blocks:
-                    counts += backend.cls(B, prefix, ptr, ext)
-                comm.all_reduce(counts, "sum")
-                ok = counts >= keep
-                rowsF.append(torch.cat([prefix[owner[ok]], ext[ok].reshape(-1, 1)], 1))
-                rowsS.append(counts[ok])
-                done = int(cum[c1 - 1])
-                c0 = c1
-            if rowsF:
-                newF, newS = torch.cat(rowsF), torch.cat(rowsS)
-            else:
-                newF = torch.zeros((0, L + 1), dtype=torch.int32, device=dev)
-                newS = torch.zeros(0, dtype=torch.int64, device=dev)
+            newF, newS = count_level(cum, lambda c0, c1: expand_classes(F, cls[c0:c1], cnt[c0:c1]),
+                                     lambda B, lo, hi, *cand: backend.cls(B, *cand), blocks, budget, keep, L + 1)
         L += 1
-        _sync()
         if stats is not None:
+            if dev.type == "cuda":
+                torch.cuda.synchronize(dev)
             stats.append({"level": L, "candidates": int(n_cand), "kept": int(newF.shape[0]), "path": path,
                           "seconds": time.perf_counter() - t0, "bitmap_seconds": blocks.seconds,
                           "row_blocks": len(blocks)})
@@ -404,4 +419,4 @@ def mine(crow: torch.Tensor, item: torch.Tensor, m: int, item_sup: torch.Tensor,
             break
         F = newF.contiguous()
         levels.append((F, newS))
-    return _result()
+    return pattern_columns(levels, dev)

@@ -29,13 +29,11 @@ size) and ``_lib.kernels_enabled()`` (no quiet fall-back).
 """
 from __future__ import annotations
 
-import os
 import time
 from typing import Callable, List, NamedTuple, Optional, Tuple
 
 import torch
 
-from ..parallel import comm
 from . import _lib
 from . import fpm as F
 
@@ -47,19 +45,13 @@ SPM_MIN_ROWS = 512              # rows (over all ranks) from which the device pa
 #                                 against the host path, between 300 rows (host 5.7 ms, device 9.7 ms) and 1000 rows
 #                                 (17.0 ms, 8.5 ms) at minSupportPercent 0.05; profiles/prefixspan.txt records the run
 WIDTHS = (8, 16, 32, 64)        # bits of a sequence's field
-_CAND_BYTES = 32                # per candidate of a batch: code, owner, count and the kept rows
 
 
 def device_selected(device, n_rows: int) -> bool:
     """True when ``PrefixSpanBatchOp`` runs on the device: a CUDA device, not switched off by
     ``ALINK_PREFIXSPAN_HIP=0``, ``n_rows >= SPM_MIN_ROWS`` unless ``ALINK_PREFIXSPAN_HIP=1`` forces it, and the
     kernel library by the one fall-back rule (``_lib.kernels_enabled``: a missing library is an error)."""
-    flag = os.environ.get("ALINK_PREFIXSPAN_HIP", "")
-    if torch.device(device).type != "cuda" or flag == "0":
-        return False
-    if flag != "1" and int(n_rows) < SPM_MIN_ROWS:
-        return False
-    return _lib.kernels_enabled()
+    return _lib.sized_gate("ALINK_PREFIXSPAN_HIP", device, n_rows, SPM_MIN_ROWS)
 
 
 def field_width(longest: int) -> int:
@@ -108,23 +100,10 @@ def _check_seq(B, n_seq, w, prefix, cls_ptr, ext) -> Tuple[int, int, int]:
     m, W = F._check_bitmap(B, "seq_counts")
     if int(w) not in WIDTHS or int(n_seq) < 0 or W != F.row_stride(int(n_seq) * int(w)):
         raise ValueError("seq_counts: w of 8, 16, 32 or 64 and a bitmap of row_stride(n_seq * w) words are needed")
-    dev = B.device
-    if not (prefix.dtype == torch.int32 and prefix.dim() == 2 and prefix.shape[1] >= 1 and prefix.is_contiguous()
-            and cls_ptr.dtype == torch.int64 and cls_ptr.dim() == 1 and cls_ptr.is_contiguous()
-            and ext.dtype == torch.int32 and ext.dim() == 1 and ext.is_contiguous()
-            and prefix.device == dev and cls_ptr.device == dev and ext.device == dev
-            and int(cls_ptr.numel()) == int(prefix.shape[0]) + 1):
-        raise ValueError("seq_counts: prefix int32 [classes, P], cls_ptr int64 [classes + 1] and ext int32 "
-                         "[candidates] of step codes, contiguous on the bitmap's device, are needed")
-    nc, ne = int(prefix.shape[0]), int(ext.numel())
-    if int(cls_ptr[0]) != 0 or int(cls_ptr[-1]) != ne or (nc and bool((cls_ptr[1:] < cls_ptr[:-1]).any())):
-        raise ValueError("seq_counts: cls_ptr must ascend from 0 to the number of candidates")
-    for t in (prefix, ext):
-        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= 2 * m):
-            raise ValueError("seq_counts: a step code whose item lies outside the bitmap's rows")
+    nc, ne, P = F._check_grouped("seq_counts", B, prefix, cls_ptr, ext, 2 * m)      # step codes 2 * item + s
     if nc and bool(((prefix[:, 0] & 1) == 0).any()):
         raise ValueError("seq_counts: every prefix starts with an S code")
-    return nc, ne, int(prefix.shape[1])
+    return nc, ne, P
 
 
 def seq_counts(B: torch.Tensor, n_seq: int, w: int, prefix: torch.Tensor, cls_ptr: torch.Tensor, ext: torch.Tensor,
@@ -154,7 +133,7 @@ def seq_counts_twin(B: torch.Tensor, n_seq: int, w: int, prefix: torch.Tensor, c
     if ne == 0:
         return counts
     W = int(B.shape[1])
-    owner = torch.repeat_interleave(torch.arange(nc, device=dev), cls_ptr[1:] - cls_ptr[:-1], output_size=ne)
+    owner = F._owner(cls_ptr[1:] - cls_ptr[:-1], ne)
     step = max(1, (2 ** 22) // W)
     for e0 in range(0, ne, step):
         pre = prefix[owner[e0:e0 + step]].to(torch.int64)
@@ -230,7 +209,7 @@ def expand_steps(Fq: torch.Tensor, st: _Steps, c0: int, c1: int):
 
     def runs(cnt):
         total = int(cnt.sum())
-        o = torch.repeat_interleave(torch.arange(nc, device=dev), cnt, output_size=total)
+        o = F._owner(cnt, total)
         j = torch.arange(total, device=dev) - (torch.cumsum(cnt, 0) - cnt)[o]
         return o, j
 
@@ -273,22 +252,12 @@ def mine(crow: torch.Tensor, item: torch.Tensor, m: int, n_seq: int, w: int, ite
     keep = max(int(min_sup), 1)
     m, n_seq, w = int(m), int(n_seq), int(w)
     levels: List[Tuple[torch.Tensor, torch.Tensor]] = []
-
-    def _result():
-        if not levels:
-            return (torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int64, device=dev),
-                    torch.zeros(0, dtype=torch.int64, device=dev))
-        codes = torch.cat([f.reshape(-1) for f, _ in levels])
-        lens = torch.cat([torch.full((int(f.shape[0]),), int(f.shape[1]), dtype=torch.int64, device=dev)
-                          for f, _ in levels])
-        return codes, lens, torch.cat([s for _, s in levels])
-
     if m < 1:
-        return _result()
+        return F.pattern_columns(levels, dev)
     one = torch.nonzero(item_sup >= keep).reshape(-1)
     Fq = (2 * one + 1).to(torch.int32).reshape(-1, 1)
     if Fq.shape[0] == 0:
-        return _result()
+        return F.pattern_columns(levels, dev)
     levels.append((Fq, item_sup[one].to(torch.int64)))
     blocks = F._Blocks(crow, item, m, backend, budget)          # cut at multiples of 64 slots: whole fields
     L = 1
@@ -297,24 +266,9 @@ def mine(crow: torch.Tensor, item: torch.Tensor, m: int, n_seq: int, w: int, ite
         st = join_steps(Fq)
         cum = torch.cumsum(st.cnt, 0)
         n_cand = int(cum[-1])
-        cap = max(1, budget // _CAND_BYTES)
-        rowsF, rowsS = [], []
-        c0, nc, done = 0, int(Fq.shape[0]), 0
-        while c0 < nc:
-            # the last parent that still fits the batch; a single parent is the smallest batch
-            c1 = int(torch.searchsorted(cum, torch.tensor(done + cap, device=dev), right=True))
-            c1 = min(max(c1, c0 + 1), nc)
-            prefix, ptr, ext, owner = expand_steps(Fq, st, c0, c1)
-            counts = torch.zeros(int(ext.numel()), dtype=torch.int64, device=dev)
-            for (lo, hi), B in zip(blocks.bounds, blocks):
-                counts += backend.seq(B, (hi - lo) // w, w, prefix, ptr, ext)
-            comm.all_reduce(counts, "sum")
-            ok = counts >= keep
-            rowsF.append(torch.cat([prefix[owner[ok]], ext[ok].reshape(-1, 1)], 1))
-            rowsS.append(counts[ok])
-            done = int(cum[c1 - 1])
-            c0 = c1
-        newF, newS = torch.cat(rowsF), torch.cat(rowsS)
+        newF, newS = F.count_level(cum, lambda c0, c1: expand_steps(Fq, st, c0, c1),
+                                   lambda B, lo, hi, *cand: backend.seq(B, (hi - lo) // w, w, *cand),
+                                   blocks, budget, keep, L + 1)
         L += 1
         if stats is not None:
             if dev.type == "cuda":
@@ -326,7 +280,7 @@ def mine(crow: torch.Tensor, item: torch.Tensor, m: int, n_seq: int, w: int, ite
             break
         Fq = newF.contiguous()
         levels.append((Fq, newS))
-    return _result()
+    return F.pattern_columns(levels, dev)
 
 
 def decode(cols):

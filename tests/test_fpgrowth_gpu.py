@@ -95,13 +95,12 @@ def test_class_counts_equal_the_oracle(P, chunk, grid):
     assert np.array_equal(got.cpu().numpy(), H.class_oracle(D, prefix, ptr, ext))
 
 
-@pytest.mark.parametrize("skip", [True, False])
-def test_class_counts_with_all_zero_prefix_chunks(skip):
+def test_class_counts_with_all_zero_prefix_chunks():
     D, prefix, ptr, ext = _zero_half_case()
     B = _c(H.packed(D))
     zero = (B[int(prefix[0, 0]), 128:256] == 0).all() and (B[int(prefix[0, 0]), 0:128] != 0).any()
-    assert bool(zero)                                                   # the skip path has something to skip
-    got = F.class_counts(B, _c(prefix), _c(ptr), _c(ext), chunk=128, skip=skip)
+    assert bool(zero)                                                   # whole steps whose prefix AND is zero
+    got = F.class_counts(B, _c(prefix), _c(ptr), _c(ext), chunk=128)
     assert np.array_equal(got.cpu().numpy(), H.class_oracle(D, prefix, ptr, ext))
 
 
@@ -122,7 +121,7 @@ def test_grids_and_chunks_give_identical_counts():
     D, prefix, ptr, ext = _class_case(3, n=20000, seed=9)
     B, args = _c(H.packed(D)), [_c(prefix), _c(ptr), _c(ext)]
     a = F.class_counts(B, *args, chunk=128, grid=3)
-    b = F.class_counts(B, *args, chunk=512, grid=64, skip=False)
+    b = F.class_counts(B, *args, chunk=512, grid=64)
     assert torch.equal(a, b) and torch.equal(a, F.class_counts_twin(B, *args))
     Bm = _c(H.packed(H.random_bits(4, 20000, 70)))
     assert torch.equal(F.pair_counts(Bm, chunk=16, splits=1), F.pair_counts(Bm, chunk=32, splits=5))

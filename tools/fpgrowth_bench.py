@@ -12,7 +12,7 @@ joined by commas, one packed ``StringBlock``).
 * per ``--percents`` value (``minSupportPercent``, default ``maxPatternLength``): ``fp_growth_device`` by stage --
   encode, bitmap, each level with its candidates and kept itemsets -- after one warm-up run at a tenth of the rows;
 * the two count kernels on the bitmap and the largest candidate batches of that run, by variant (chunk, splits,
-  grid, skip): milliseconds (device events, best of ``--reps``), ps per (candidate, 64-bit word), and the bytes
+  grid): milliseconds (device events, best of ``--reps``), ps per (candidate, 64-bit word), and the bytes
   each variant reads from the L2 side per second, beside 6.3 TB/s (HBM, streamed) and 8.6 TB/s (Infinity Cache,
   random rows) of the MI355X -- context, not a pass mark;
 * ``--host-rows``: the host path (the operator's ``to_list`` / ``split`` / ``fp_growth`` / sort) against the device
@@ -121,11 +121,10 @@ def micro(cap, reps):
         nc, ne = int(prefix.shape[0]), int(ext.numel())
         tiles = int(((ptr[1:] - ptr[:-1] + 15) // 16).sum())
         read = (ne + tiles * P) * W * 8                         # every extension row once, the prefix rows per tile
-        for chunk, grid, skip in ((0, 0, True), (0, 0, False), (128, 0, True), (512, 0, True), (2048, 0, True),
-                                  (8192, 0, True), (0, 512, True), (0, 4096, True)):
-            ms = timed(lambda: F.class_counts(B, prefix, ptr, ext, chunk=chunk, grid=grid, skip=skip), reps)
+        for chunk, grid in ((0, 0), (128, 0), (512, 0), (2048, 0), (8192, 0), (0, 512), (0, 4096)):
+            ms = timed(lambda: F.class_counts(B, prefix, ptr, ext, chunk=chunk, grid=grid), reps)
             out.append({"kernel": "class", "prefix_len": P, "classes": nc, "candidates": ne, "words": W,
-                        "chunk": chunk, "grid": grid, "skip": skip, "ms": ms,
+                        "chunk": chunk, "grid": grid, "ms": ms,
                         "ps_per_candidate_word": ms * 1e9 / (ne * W), "l2_side_TBps": read / ms / 1e9})
     return out
 
