@@ -27,13 +27,14 @@ constexpr int kLdsBudget = 64 * 1024;  // bytes per workgroup -> 2 workgroups pe
 
 __global__ __launch_bounds__(kThreads) void tree_hist_lds(
     const uint8_t* __restrict__ bins, int64_t n, int F, const int32_t* __restrict__ slot,
-    const float* __restrict__ stats, int S, int B, int slots_per_group, int FG, int64_t rows_per_block,
+    const float* __restrict__ stats, int S, int B, int slots_per_group, int nslots, int FG, int64_t rows_per_block,
     float* __restrict__ hist) {
   extern __shared__ double sh[];   // fp64: ds_add_f64 ~9 cyc vs ds_add_f32 ~193 (K7 note below)
   const int fstride = B * S + 1;
   const int f0 = blockIdx.y * FG;
   const int fg = min(FG, F - f0);
   const int slot0 = blockIdx.z * slots_per_group;
+  const int ns = min(slots_per_group, nslots - slot0);   // the last group may reach past nslots: those rows are skipped
   const int lds_n = slots_per_group * FG * fstride;
   for (int i = threadIdx.x; i < lds_n; i += kThreads) sh[i] = 0.0;
   __syncthreads();
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(kThreads) void tree_hist_lds(
       const int f = p - rl * fg;
       const int64_t r = r0 + rl;
       const int s = slot[r] - slot0;
-      if ((unsigned)s >= (unsigned)slots_per_group) continue;
+      if ((unsigned)s >= (unsigned)ns) continue;
       const int b = bins[r * F + f0 + f];
       double* h = sh + (s * FG + f) * fstride + b * S;
       const float* st = stats + r * S;
@@ -81,13 +82,14 @@ __global__ __launch_bounds__(kThreads) void tree_hist_lds(
 template <int S>
 __global__ __launch_bounds__(kThreads) void tree_hist_rows(
     const uint8_t* __restrict__ bins, int64_t n, int F, const int32_t* __restrict__ slot,
-    const float* __restrict__ stats, int B, int slots_per_group, int FG, int64_t rows_per_block,
+    const float* __restrict__ stats, int B, int slots_per_group, int nslots, int FG, int64_t rows_per_block,
     float* __restrict__ hist) {
   extern __shared__ double sh[];   // fp64: ds_add_f64 ~9 cyc vs ds_add_f32 ~193 (K7 note below)
   const int fstride = B * S + 1;
   const int f0 = blockIdx.y * FG;
   const int fg = min(FG, F - f0);
   const int slot0 = blockIdx.z * slots_per_group;
+  const int ns = min(slots_per_group, nslots - slot0);   // the last group may reach past nslots: those rows are skipped
   const int lds_n = slots_per_group * FG * fstride;
   for (int i = threadIdx.x; i < lds_n; i += kThreads) sh[i] = 0.0;
   __syncthreads();
@@ -95,7 +97,7 @@ __global__ __launch_bounds__(kThreads) void tree_hist_rows(
   const int64_t r1 = min(n, r0 + rows_per_block);
   for (int64_t r = r0 + threadIdx.x; r < r1; r += kThreads) {
     const int s = slot[r] - slot0;
-    if ((unsigned)s >= (unsigned)slots_per_group) continue;
+    if ((unsigned)s >= (unsigned)ns) continue;
     double v[S];
 #pragma unroll
     for (int k = 0; k < S; ++k) v[k] = (double)stats[r * S + k];
@@ -460,7 +462,8 @@ int alink_tree_node_sums(const int32_t* node, const uint8_t* sample, const float
 }
 
 
-// hist must be zeroed by the caller: [nslots, F, B, S] fp32.
+// hist must be zeroed by the caller: [nslots, F, B, S] fp32.  Rows with a slot outside [0, nslots) are skipped by
+// every kernel (the last slot group's LDS range may reach past nslots); every bin must be < B.
 // variant bit 0: use the (row, feature)-pair kernel instead of the row-per-lane kernel.
 int alink_tree_hist_f32(const uint8_t* bins, int64_t n, int F, const int32_t* slot, const float* stats,
                         int S, int B, int nslots, float* hist, int num_cus, int variant, hipStream_t stream) {
@@ -502,16 +505,16 @@ int alink_tree_hist_f32(const uint8_t* bins, int64_t n, int F, const int32_t* sl
   const dim3 grid((unsigned)gx, gy, groups);
   if (S >= 2 && S <= 4 && !(variant & 1)) {
     if (S == 2)
-      hipLaunchKernelGGL(tree_hist_rows<2>, grid, dim3(kThreads), lds, stream, bins, n, F, slot, stats, B, spg, FG,
+      hipLaunchKernelGGL(tree_hist_rows<2>, grid, dim3(kThreads), lds, stream, bins, n, F, slot, stats, B, spg, nslots, FG,
                          rows_per_block, hist);
     else if (S == 3)
-      hipLaunchKernelGGL(tree_hist_rows<3>, grid, dim3(kThreads), lds, stream, bins, n, F, slot, stats, B, spg, FG,
+      hipLaunchKernelGGL(tree_hist_rows<3>, grid, dim3(kThreads), lds, stream, bins, n, F, slot, stats, B, spg, nslots, FG,
                          rows_per_block, hist);
     else
-      hipLaunchKernelGGL(tree_hist_rows<4>, grid, dim3(kThreads), lds, stream, bins, n, F, slot, stats, B, spg, FG,
+      hipLaunchKernelGGL(tree_hist_rows<4>, grid, dim3(kThreads), lds, stream, bins, n, F, slot, stats, B, spg, nslots, FG,
                          rows_per_block, hist);
   } else {
-    hipLaunchKernelGGL(tree_hist_lds, grid, dim3(kThreads), lds, stream, bins, n, F, slot, stats, S, B, spg, FG,
+    hipLaunchKernelGGL(tree_hist_lds, grid, dim3(kThreads), lds, stream, bins, n, F, slot, stats, S, B, spg, nslots, FG,
                        rows_per_block, hist);
   }
   return hipGetLastError() == hipSuccess ? 0 : 2;

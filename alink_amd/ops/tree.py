@@ -277,7 +277,9 @@ def fm_eligible(bins: torch.Tensor, S: int, B: int, variant: int = None, pack: b
 def histogram(bins: torch.Tensor, slot: torch.Tensor, stats: torch.Tensor, nslots: int, B: int,
               variant: int = None, prep: FmStats = None, tro: "RowOrder" = None, slot_nodes=None) -> torch.Tensor:
     """[nslots, F, B, S] histogram (fp32 on GPU via HIP, fp64 on CPU).  ``prep``: the statistics already
-    quantised for the fixed-point kernel (``FmStats(stats)``, reused across the levels of a tree)."""
+    quantised for the fixed-point kernel (``FmStats(stats)``, reused across the levels of a tree).  Rows whose slot
+    is outside ``[0, nslots)`` are skipped.
+    Every bin must be ``< B``: the fp32-atomic kernels index LDS with the raw bin."""
     if not bins.is_cuda:
         return histogram_torch(bins, slot, stats, nslots, B)
     if not _lib.kernels_enabled():
