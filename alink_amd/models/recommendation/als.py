@@ -372,7 +372,8 @@ def als_topk(model: AlsModelData, users: Sequence[int], k: int, device) -> List[
 
     This rank's users stay on its device; the item table is split into one block per rank and the blocks
     rotate around the RCCL ring (``parallel/cross.py``), each merged by the fused score + top-K kernel, so no
-    rank materialises a score matrix or more than two item blocks.  Output ``"item:score,..."``."""
+    rank materialises a score matrix or more than two item blocks.  Output ``"item:score,..."``, best first;
+    equal scores rank by the item's row in the model's item table, on every device and rank count."""
     want = [int(x) for x in users if x is not None and int(x) in model.user_map]
     seen, uniq = set(), []
     for x in want:

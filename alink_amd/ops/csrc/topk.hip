@@ -13,16 +13,25 @@
 //     items x 4 dims, B = 4 dims x 16 queries; the query fragment stays in VGPRs for the whole launch.  The
 //     k dimension is permuted (lane group g supplies dims 16s+4g+e) so one b128 read feeds 4 MFMAs;
 //   * each query's top-K lives in LDS ([K][16] per wave, query-minor -> conflict-free scans) with its
-//     current minimum as the admission threshold held in registers.  The common case is a wave-wide ballot
-//     of "score > threshold" that comes back empty; candidates replace the minimum and trigger one
-//     cooperative rescan (each lane group scans K/4 slots, two lane swaps combine them).
+//     current minimum (score and id) as the admission threshold held in registers.  The common case is a
+//     wave-wide ballot of "beats the threshold" that comes back empty; candidates replace the minimum and
+//     trigger one cooperative rescan (each lane group scans K/4 slots, two lane swaps combine them).
 //
 // The state (best_val / best_idx, [m][K], unsorted) is read at launch start and written at the end, so a
-// ring of item blocks (parallel/cross.py) continues the same top-K across launches.  Ties keep the earlier
-// entry (strict '>' admission, as the reference's PriorityQueue replace rule).
+// ring of item blocks (parallel/cross.py) continues the same top-K across launches.
+//
+// Order (inputs finite; NaN and infinite scores are out of scope): entry (s, id) ranks before (s', id') iff
+// s > s', or s == s' and id < id'.  After any sequence of launches the state holds, per query, the first
+// min(K, N) of all (score, global id) pairs seen in that order, and (-inf, -1) in the remaining slots: the
+// result depends on the union of the items with their global ids, not on how they were split into launches
+// or slices nor on the order of the launches (a ring delivers blocks in owner order, not id order).  So the
+// tracked minimum is the smallest score and, among equal scores, the largest id, and a candidate is admitted
+// iff it ranks before that minimum.  A score equal to the threshold can only win with a smaller id, so a lane
+// looks at equal scores only in chunks whose ids reach below its threshold's id: blocks merged in ascending
+// id order never do, and ties there stay on the one-ballot fast path.
 //
 // Small query sets are split over items as well (grid.y = item slices, one state plane each, merged on the
-// host by one topk over [m][slices*K]) so that a launch always has >= 2 workgroups per CU.
+// host in the same two-key order over [m][slices*K]) so that a launch always has >= 2 workgroups per CU.
 //
 // Contract (checked by the host wrapper): R in {16, 32, 48, 64} (rank zero-padded), 1 <= K <= 128, Q [m][R]
 // and T [n][R] row-major fp32, 16-B aligned; item indices (item_base + row) < 2^31.
@@ -46,21 +55,58 @@ struct Cfg {
     static constexpr int LOADS = (IT * R / 4 + WAVES * 64 - 1) / (WAVES * 64);   // float4 loads / thread / chunk
 };
 
-// minimum (value, slot) of this lane's query over all K slots: lane group g scans slots g, g+4, ...
-__device__ __forceinline__ void rescan(const float* tv, int K, int j, int g, float& thr, int& pos) {
-    float mv = 3.4e38f;
+// last-ranked (value, id, slot) of this lane's query over all K slots: the smallest value, among equal values
+// the largest id.  Lane group g scans slots g, g+4, ... and may own none (K < 4): it starts from +inf, which
+// every real entry undercuts.  The scan runs once per admission and is most of the kernel's time on ordinary
+// data, so it reads the values only (4 slots per trip) and notes whether the minimum occurs twice; the ids are
+// read in a second pass only when some query's finite minimum does (equal -inf are the (-inf, -1) fillers:
+// the lowest slot, so the 4 lane groups agree).
+__device__ __forceinline__ void rescan(const float* tv, const int* ti, int K, int j, int g, float& thr, int& tid,
+                                       int& pos) {
+    const float INF = __builtin_inff();
+    float mv = INF;
     int mp = 0;
-    for (int kk = g; kk < K; kk += 4) {
-        const float v = tv[kk * QW + j];
-        if (v < mv) { mv = v; mp = kk; }
+    int dup = 0;                                          // 0 / 1, kept in arithmetic so the loop stays branch-free
+    for (int k0 = g; k0 < K; k0 += 16) {
+        float v[4];                                       // 4 slots per trip: their LDS reads are in flight together
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int kk = k0 + 4 * u;
+            const float x = tv[(kk < K ? kk : k0) * QW + j];
+            v[u] = kk < K ? x : INF;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int lt = v[u] < mv, eq = v[u] == mv;
+            dup = eq | (dup & (lt ^ 1));
+            mv = lt ? v[u] : mv;
+            mp = lt ? k0 + 4 * u : mp;
+        }
     }
 #pragma unroll
     for (int sh = 16; sh <= 32; sh <<= 1) {
         const float ov = __shfl_xor(mv, sh);
         const int op = __shfl_xor(mp, sh);
-        if (ov < mv || (ov == mv && op < mp)) { mv = ov; mp = op; }
+        const int od = __shfl_xor(dup, sh);
+        const int lt = ov < mv, eq = ov == mv;
+        dup = eq | (lt ? od : dup);
+        if (lt || (eq && op < mp)) { mv = ov; mp = op; }
+    }
+    if (__ballot(dup != 0 && mv > -INF && mv < INF) != 0) {
+        int mi = INT32_MIN;                               // below every id: a group without the minimum loses
+        for (int kk = g; kk < K; kk += 4) {
+            const int i = ti[kk * QW + j];
+            if (tv[kk * QW + j] == mv && i > mi) { mi = i; mp = kk; }
+        }
+#pragma unroll
+        for (int sh = 16; sh <= 32; sh <<= 1) {
+            const int oi = __shfl_xor(mi, sh);
+            const int op = __shfl_xor(mp, sh);
+            if (oi > mi || (oi == mi && op < mp)) { mi = oi; mp = op; }
+        }
     }
     thr = mv;
+    tid = ti[mp * QW + j];
     pos = mp;
 }
 
@@ -111,12 +157,12 @@ __global__ __launch_bounds__(512) void topk_cross_kernel(const float* __restrict
     }
     // running state -> LDS (padding queries get +inf: nothing is ever admitted for them)
     for (int kk = g; kk < K; kk += 4) {
-        tv[kk * QW + j] = qok ? best_val[q * K + kk] : 3.4e38f;
+        tv[kk * QW + j] = qok ? best_val[q * K + kk] : __builtin_inff();
         ti[kk * QW + j] = qok ? best_idx[q * K + kk] : -1;
     }
     float thr;
-    int pos;
-    rescan(tv, K, j, g, thr, pos);
+    int thr_id, pos;
+    rescan(tv, ti, K, j, g, thr, thr_id, pos);
 
     const int64_t nchunks = (n + IT - 1) / IT;
     f32x4 pre[C::LOADS];
@@ -161,9 +207,21 @@ __global__ __launch_bounds__(512) void topk_cross_kernel(const float* __restrict
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 if (acc[t][r] > thr && row0 + 16 * t + 4 * g + r < n) mask |= 1u << (4 * t + r);
-        if (__ballot(mask != 0) == 0) continue;           // fast path: nothing beats any threshold
+        // an equal score wins only with an id below the threshold's: possible only if this lane's first id of
+        // the chunk is below it (never when blocks arrive in ascending id order)
+        const bool tie_ok = (int64_t)thr_id > (int64_t)item_base + row0 + 4 * g;
+        if (__ballot(mask != 0 || tie_ok) == 0) continue;  // fast path: nothing beats any threshold
+        if (tie_ok) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (acc[t][r] == thr && row0 + 16 * t + 4 * g + r < n) mask |= 1u << (4 * t + r);
+        }
+        if (__ballot(mask != 0) == 0) continue;
         // slow path: lane group by lane group (the 4 groups of a query must not race on its slots), each lane
-        // walks only its own set bits
+        // walks only its own set bits.  The walk is not in id order; the exact (score, id) admission and the
+        // eviction of the exact minimum make the surviving set independent of the order.
         for (int gg = 0; gg < 4; ++gg) {
             uint32_t mm = g == gg ? mask : 0u;
             while (__ballot(mm != 0u) != 0) {
@@ -175,14 +233,14 @@ __global__ __launch_bounds__(512) void topk_cross_kernel(const float* __restrict
                     mm &= mm - 1u;
                     sc = pick16(acc, b);
                     idx = item_base + (int)(row0 + 4 * g + 16 * (b >> 2) + (b & 3));
-                    mine = sc > thr;
+                    mine = sc > thr || (sc == thr && idx < thr_id);
                 }
                 if (__ballot(mine) == 0) continue;
                 if (mine) {
                     tv[pos * QW + j] = sc;
                     ti[pos * QW + j] = idx;
                 }
-                rescan(tv, K, j, g, thr, pos);
+                rescan(tv, ti, K, j, g, thr, thr_id, pos);
             }
         }
     }

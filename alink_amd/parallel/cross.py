@@ -35,6 +35,11 @@ def blockwise_topk(Q: torch.Tensor, T_local: torch.Tensor, K: int, descending: b
 
     ``T_local`` is this rank's block [n_p, r]; the global id of its row i is ``sum(n_q for q < p) + i``.
     Returns ``(scores [m, K], ids [m, K] int64)`` sorted best first (ids -1 where fewer than K items exist).
+
+    Equal scores rank by ascending global id (the order of ``ops/topk.py``), so the result depends only on the
+    queries, the items with their global ids and ``K``: not on the number of ranks or the order in which the
+    ring delivers the blocks.  ``descending=False`` is the same rule on ``-Q``.  Scores are finite; NaN and
+    infinite scores are out of scope.
     """
     dev = Q.device
     Qs = Q.to(torch.float32) if descending else -Q.to(torch.float32)

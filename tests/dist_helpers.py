@@ -259,6 +259,14 @@ def scenario_cross(out):
     for desc in (True, False):
         v, i = blockwise_topk(Q[qb[me]:qb[me + 1]], T[ib[me]:ib[me + 1]], 7, descending=desc)
         out["desc" if desc else "asc"] = {"v": v.tolist(), "i": i.tolist(), "q0": qb[me]}
+    # integer, tie-rich: the ids are fixed by the (score, id) order, whatever the number of ranks
+    import topk_helpers
+    Qi, Ti = topk_helpers.tie_rich(3, 37, 53, 3)
+    Qi[4] = Qi[30] = 0
+    Qi, Ti = topk_helpers.f32(Qi), topk_helpers.f32(Ti)
+    for desc in (True, False):
+        v, i = blockwise_topk(Qi[qb[me]:qb[me + 1]], Ti[ib[me]:ib[me + 1]], 7, descending=desc)
+        out["int_desc" if desc else "int_asc"] = {"v": v.tolist(), "i": i.tolist(), "q0": qb[me]}
 
 
 def run(rank, world, port, scenario, outdir):

@@ -308,6 +308,13 @@ def scenario_cross_gpu(out):
     out["ids_equal"] = bool(torch.equal(i.cpu(), ref_i))
     out["max_abs_diff"] = float((v.cpu() - ref_v).abs().max())
     out["on_device"] = v.is_cuda
+    # integer, tie-rich: the ids are fixed by the (score, id) order, whatever the number of ranks
+    import topk_helpers
+    Qi, Ti = topk_helpers.tie_rich(3, 300, 5000, 16)
+    Qi[11] = Qi[299] = 0
+    Qi, Ti = topk_helpers.f32(Qi), topk_helpers.f32(Ti)
+    v, i = blockwise_topk(Qi[qb[me]:qb[me + 1]].to(dev), Ti[ib[me]:ib[me + 1]].to(dev), 10)
+    out["int"] = {"v": v.tolist(), "i": i.tolist(), "q0": qb[me]}
 
 
 def run(rank, world, port, scenario, outdir):

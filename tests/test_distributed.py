@@ -182,6 +182,21 @@ def test_blockwise_topk_ring(tmp_path, world):
                 order = np.argsort(-S[q] if desc else S[q], kind="stable")[:7]
                 np.testing.assert_allclose(vals, S[q][order], rtol=1e-5, atol=1e-5)
                 assert sorted(ids) == sorted(order.tolist())
+    # integer, tie-rich data: values and ids exactly the oracle's, so world 1 and world 3 agree
+    import topk_helpers
+    Qi, Ti = topk_helpers.tie_rich(3, 37, 53, 3)
+    Qi[4] = Qi[30] = 0
+    for key, sign in (("int_desc", 1), ("int_asc", -1)):
+        rv, ri = topk_helpers.topk_oracle(sign * Qi, Ti, 7)
+        assert ri[4].tolist() == list(range(7))
+        rows = 0
+        for o in outs:
+            part = o[key]
+            q0, k = part["q0"], len(part["i"])
+            assert part["i"] == ri[q0:q0 + k].tolist()
+            assert part["v"] == (sign * rv[q0:q0 + k]).tolist()
+            rows += k
+        assert rows == 37
 
 
 def test_glm_two_processes_equal_single(tmp_path):

@@ -186,5 +186,19 @@ def test_ftrl_stream_pipeline_multiprocess_gpu(tmp_path, mode, monkeypatch):
 
 def test_ring_topk_multiprocess_gpu(tmp_path):
     """Ring blockwise top-K with device blocks over 2 ranks == torch.topk of the full score matrix."""
-    for o in _run("cross_gpu", 2, tmp_path):
+    outs = _run("cross_gpu", 2, tmp_path)
+    for o in outs:
         assert o["on_device"] and o["ids_equal"] and o["max_abs_diff"] < 1e-4
+    # integer, tie-rich data: values and ids exactly the oracle's, whatever the split over the ranks
+    import topk_helpers
+    Qi, Ti = topk_helpers.tie_rich(3, 300, 5000, 16)
+    Qi[11] = Qi[299] = 0
+    rv, ri = topk_helpers.topk_oracle(Qi, Ti, 10)
+    assert ri[11].tolist() == list(range(10))
+    rows = 0
+    for o in outs:
+        q0, k = o["int"]["q0"], len(o["int"]["i"])
+        assert o["int"]["i"] == ri[q0:q0 + k].tolist()
+        assert o["int"]["v"] == rv[q0:q0 + k].tolist()
+        rows += k
+    assert rows == 300
