@@ -22,7 +22,7 @@ from typing import Dict, List, Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, csr
 
 __all__ = ["TreeTable", "tree_table", "descend_f64", "descend_csr", "BISECT_CALLS"]
 
@@ -124,10 +124,6 @@ def descend_csr(fm, table: TreeTable, slot: torch.Tensor, levels: int, grid: int
     _check(table, slot, n, d, fm.val.device)
     if n == 0 or levels <= 0 or table.P == 0:
         return slot
-    crow, col, val = fm.crow.contiguous(), fm.col.contiguous(), fm.val.contiguous()
-    if int(crow.numel()) != n + 1 or col.numel() != val.numel():
-        raise ValueError("malformed CSR matrix")
-    _launch("alink_bisect_descend_csr", table,
-            [crow.data_ptr(), col.data_ptr(), int(col.dtype == torch.int64), val.data_ptr(), n, d], slot, levels,
-            grid, val.device)
+    alive, head = csr.row_args(fm, d)      # alive: the arrays behind head's pointers
+    _launch("alink_bisect_descend_csr", table, head, slot, levels, grid, fm.val.device)
     return slot

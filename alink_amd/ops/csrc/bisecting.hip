@@ -21,12 +21,17 @@
 //   row gets the same side in every launch.  The row stays in registers across the levels (16 doubles per lane at
 //   d = 1024); a row whose slot does not descend is not read.  The planes come from the table through L2.
 // * alink_bisect_descend_csr — the same for CSR rows (crow int64, col int32 / int64, val fp64) that are never
-//   densified: one wave per row, lane l takes the entries l, l + 64, ... in ascending order, the same butterfly.
-//   Entries whose column is outside [0, d) are skipped.
+//   densified: one wave per row, lane l takes the entries l, l + 64, ... in ascending order, the same butterfly
+//   (lane_bcast.h: group_sum).  Entries whose column is outside [0, d) are skipped.  The grid and the column-type
+//   dispatch are those of the CSR row kernels (csr_rows.h, host side).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "csr_rows.h"
+
 namespace {
+
+using lane::group_sum;
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
 
@@ -35,15 +40,6 @@ constexpr int BD_THREADS = 256;
 #define BD_PAIRS_IN_FLIGHT 4
 #endif
 constexpr int BD_FLIGHT = BD_PAIRS_IN_FLIGHT;   // 16-byte loads of X a lane has in flight: R rows of NP pairs each
-
-// the sum of the G lanes' values (G a power of two, groups aligned to G): both partners of a step add the same two
-// values, so every lane of the group ends with the same bits
-template <int G>
-__device__ __forceinline__ double group_sum(double a) {
-#pragma unroll
-    for (int o = 1; o < G; o <<= 1) a += __shfl_xor(a, o, 64);
-    return a;
-}
 
 // the lane's NP pairs of the d-vector at p (pairs g, g + G, ...); elements at or past d are zero and not loaded
 template <int G, int NP, bool VEC>
@@ -143,7 +139,7 @@ __global__ __launch_bounds__(BD_THREADS) void bisect_descend_f64_kernel(
     }
 }
 
-constexpr int BC_WAVES = 4;
+constexpr int BC_WAVES = csr::WAVES;       // the launch of csr_rows.h
 
 template <typename I>
 __global__ __launch_bounds__(64 * BC_WAVES) void bisect_descend_csr_kernel(
@@ -271,18 +267,9 @@ int alink_bisect_descend_csr(const int64_t* crow, const void* col, int idx64, co
     if (n <= 0 || levels <= 0 || S <= 0) return 0;
     if (d < 1 || P0 == nullptr || (cosine ? P1 == nullptr : thr == nullptr)) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    int64_t blocks = (n + BC_WAVES - 1) / BC_WAVES;
-    const int64_t cap = grid > 0 ? grid : 16384;
-    if (blocks > cap) blocks = cap;
-    const dim3 g((unsigned)blocks), b(64 * BC_WAVES);
-    if (idx64)
-        hipLaunchKernelGGL((bisect_descend_csr_kernel<int64_t>), g, b, 0, st, crow,
-                           reinterpret_cast<const int64_t*>(col), val, n, d, slot, S, left, right, P0, P1, thr, cosine,
-                           levels);
-    else
-        hipLaunchKernelGGL((bisect_descend_csr_kernel<int32_t>), g, b, 0, st, crow,
-                           reinterpret_cast<const int32_t*>(col), val, n, d, slot, S, left, right, P0, P1, thr, cosine,
-                           levels);
+    ALINK_CSR_LAUNCH_IDX((bisect_descend_csr_kernel<int64_t>), (bisect_descend_csr_kernel<int32_t>), idx64,
+                         csr::wave_blocks(n, grid, BC_WAVES, csr::WAVE_GRID), st, crow, col, val, n, d, slot, S, left,
+                         right, P0, P1, thr, cosine, levels);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

@@ -26,34 +26,28 @@
 //   Choices: LDS 4 NT KiB per workgroup (<= 32 KiB, so LDS never limits below 5 workgroups per CU); 256-thread
 //   workgroups so that one staged block serves 64 rows; the grid is capped at 1024 workgroups that stride over the
 //   row batches.
-// * alink_evalcluster_rows_csr — CSR rows (int32 / int64 columns), one wave per row, as sparse_nearest_kernel
-//   (kmeans_sparse.hip): the means come transposed and padded, Mt [d, kp], lane l owns clusters l, l + 64, ... of a
-//   block of up to 256 clusters, 64 entries are loaded at a time and walked in stored order with wave-uniform
-//   broadcasts, U gathers in flight; k > 256 loops over cluster blocks.  Entries whose column is outside [0, d)
-//   become (column 0, value 0) before any address is formed and add nothing, to the dots and to the norms alike.
+// * alink_evalcluster_rows_csr — CSR rows (int32 / int64 columns), one wave per row, on the row walk of csr_rows.h
+//   (the table is the cluster means, transposed and padded, Mt [d, kp]; the lane / cluster map and the entry guard
+//   are described there): per cluster block the walk gives the lane's dots and |x|^2, and this file keeps ev_dis,
+//   the min, the own dot and ev_store.  Entries whose column is outside [0, d) add nothing, to the dots and to the
+//   norms alike.
 //   own never touches d elements: with the per-cluster |m|^2 and sum |m| (stat columns 3, 4)
 //     EUCLIDEAN  sqrt(max(0, |m|^2 + sum_nz((x_j - m_j)^2 - m_j^2))),
 //     CITYBLOCK  sum |m| + sum_nz(|x_j - m_j| - |m_j|),
 //     COSINE     1 - x.m / (|x| |m|) from the own dot,
-//   where m_j = Mt[j, cid] is one wave-uniform load per entry.  A row must store a column at most once.
+//   where m_j = Mt[j, cid] is one wave-uniform load per entry, taken through the walk's per-entry hook (own_terms)
+//   during the first cluster block.  A row must store a column at most once.
 //   Every lane walks the entries in stored order, so a row's values do not depend on the grid.
 //   Choices: no LDS (the table rows are read once per entry, coalesced over the lanes); 4 rows per 256-thread
 //   workgroup; up to 16384 workgroups striding over the rows.
 // Non-finite rows are not guaranteed (a NaN dot is skipped by the min).  Plain C++ and vector stores only.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+#include "csr_rows.h"
 #include "dense64_mfma.h"
-#include "lane_bcast.h"
 
 namespace {
 
 using namespace d64;
-using lane::bcast_f64;
-using lane::bcast_i64;
 
-constexpr int EV_CSR_WAVES = 4;      // waves (rows) per workgroup of the CSR kernel
-constexpr int EV_NB = 4;             // cluster blocks of 64 a lane of the CSR kernel holds at most
 constexpr int EV_STAT = 8;           // doubles per cluster record: cnt, n2, 1 / max(cnt, 1), |m|^2, sum |m|, padding
 
 // dis_j of the closed form from the dot x.m_j
@@ -186,18 +180,31 @@ __global__ __launch_bounds__(64 * WAVES) void evalcluster_rows_f64_kernel(
     }
 }
 
+// The hook of the CSR walk (csr_rows.h) that sums own's entry terms from m = Mt[c, own], one wave-uniform load per
+// entry: (v - m)^2 - m^2 (dist 0) or |v - m| - |m| (dist 2).  A (0, 0.0) entry gives exactly 0 either way.
+struct own_terms {
+    bool on;            // the first cluster block's walk alone, EUCLIDEAN and CITYBLOCK
+    int own, dist;
+    double oacc;
+    __device__ __forceinline__ double gather(const double* __restrict__ rowp) const { return on ? rowp[own] : 0.0; }
+    __device__ __forceinline__ void fold(double v, double m) {
+        if (on) {
+            const double df = v - m;
+            oacc += dist == 0 ? df * df - m * m : fabs(df) - fabs(m);
+        }
+    }
+};
+
 // Mt [d, kp]; stat [kp, 8] = (cnt, n2, 1 / max(cnt, 1), |m|^2, sum |m|, ...), zero on the padded clusters.
-// NB: cluster blocks of 64 per pass (kp >= 64 * NB unless NB == EV_NB, where the tail block is guarded);
-// U: entries whose gathers are issued together.
+// NB, U: cluster blocks of 64 per pass and entries whose gathers are issued together (csr_rows.h).
 template <int NB, int U, typename I>
-__global__ __launch_bounds__(64 * EV_CSR_WAVES) void evalcluster_rows_csr_kernel(
+__global__ __launch_bounds__(64 * csr::WAVES) void evalcluster_rows_csr_kernel(
         const int64_t* __restrict__ crow, const I* __restrict__ col, const double* __restrict__ val, int64_t n,
         int64_t d, const int* __restrict__ cid, const double* __restrict__ Mt, const double* __restrict__ stat, int k,
         int kp, int dist, double* __restrict__ out) {
     const int lane = threadIdx.x & 63;
-    const int64_t w0 = (int64_t)blockIdx.x * EV_CSR_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t nw = (int64_t)gridDim.x * EV_CSR_WAVES;
-    for (int64_t r = w0; r < n; r += nw) {
+    const int64_t nw = csr::item_stride();
+    for (int64_t r = csr::first_item(); r < n; r += nw) {
         const int64_t s = crow[r], e = crow[r + 1];
         const int own = __builtin_amdgcn_readfirstlane(cid[r]);
         const bool own_ok = own >= 0 && own < k;
@@ -210,67 +217,24 @@ __global__ __launch_bounds__(64 * EV_CSR_WAVES) void evalcluster_rows_csr_kernel
             }
             continue;
         }
-        const bool rearranged = dist != 1;      // own through the gathered m_j (EUCLIDEAN, CITYBLOCK)
         double nb = __builtin_inf();
         double owndot = 0.0;
         double xn = 0.0;
         double oacc = 0.0;
         for (int cb = 0; cb < kp; cb += 64 * NB) {
-            double acc[NB];
-#pragma unroll
-            for (int b = 0; b < NB; ++b) acc[b] = 0.0;
-            xn = 0.0;
-            const bool with_own = rearranged && cb == 0;
-            for (int64_t p = s; p < e; p += 64) {
-                const int m = (int)((e - p) < 64 ? (e - p) : 64);
-                // guarded entry of this lane: an out-of-range column (or a lane past the row) becomes (0, 0.0)
-                int64_t cj = 0;
-                double vj = 0.0;
-                if (lane < m) {
-                    const int64_t c = (int64_t)col[p + lane];
-                    if (c >= 0 && c < d) {
-                        cj = c;
-                        vj = val[p + lane];
-                    }
-                }
-                for (int j0 = 0; j0 < m; j0 += U) {
-                    double v[U];
-                    double mo[U];
-                    double t[U][NB];
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        // lanes j0 + u >= m hold (0, 0.0): they read row 0 of Mt and add nothing
-                        const int j = (j0 + u) & 63;
-                        const int64_t c = bcast_i64(cj, j);
-                        v[u] = bcast_f64(vj, j);
-                        const double* __restrict__ rowp = Mt + c * (int64_t)kp;
-                        mo[u] = with_own ? rowp[own] : 0.0;
-#pragma unroll
-                        for (int b = 0; b < NB; ++b)
-                            t[u][b] = (NB < EV_NB || cb + 64 * b < kp) ? rowp[cb + lane + 64 * b] : 0.0;
-                    }
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        xn = fma(v[u], v[u], xn);
-                        // a (0, 0.0) entry gives (0 - m)^2 - m^2 = 0 and |0 - m| - |m| = 0 exactly
-                        if (with_own) {     // the first cluster block's walk alone
-                            const double df = v[u] - mo[u];
-                            oacc += dist == 0 ? df * df - mo[u] * mo[u] : fabs(df) - fabs(mo[u]);
-                        }
-#pragma unroll
-                        for (int b = 0; b < NB; ++b) acc[b] = fma(v[u], t[u][b], acc[b]);
-                    }
-                }
-            }
+            const auto w = csr::row_dots<NB, U, csr::NBMAX>(col, val, s, e, d, Mt, kp, cb, lane,
+                                                            own_terms{dist != 1 && cb == 0, own, dist, oacc});
+            xn = w.xn;
+            oacc = w.hook.oacc;
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
                 const int c = cb + 64 * b + lane;
-                if ((NB < EV_NB || cb + 64 * b < kp) && c < k) {
+                if ((NB < csr::NBMAX || cb + 64 * b < kp) && c < k) {
                     if (c == own) {
-                        owndot = acc[b];
+                        owndot = w.acc[b];
                     } else {
                         const double* __restrict__ sc = stat + EV_STAT * c;
-                        double v = ev_dis(dist, acc[b], xn, sc[0], sc[1]);
+                        double v = ev_dis(dist, w.acc[b], xn, sc[0], sc[1]);
                         if (dist == 0) v = v * sc[2];
                         if (v < nb) nb = v;
                     }
@@ -336,23 +300,8 @@ int alink_evalcluster_rows_csr(const int64_t* crow, const void* col, int idx64, 
     if (d < 1 || k < 1 || kp < 64 || kp % 64 != 0 || k > kp || n >= (1ll << 31)) return 1;
     if (dist < 0 || dist > 2) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    int64_t blocks = (n + EV_CSR_WAVES - 1) / EV_CSR_WAVES;
-    const int64_t cap = grid > 0 ? grid : 16384;
-    if (blocks > cap) blocks = cap;
-    const dim3 g((unsigned)blocks), b(64 * EV_CSR_WAVES);
-#define ALINK_EV_CSR(NB, U)                                                                                        \
-    do {                                                                                                           \
-        if (idx64)                                                                                                 \
-            hipLaunchKernelGGL((evalcluster_rows_csr_kernel<NB, U, int64_t>), g, b, 0, st, crow,                   \
-                               reinterpret_cast<const int64_t*>(col), val, n, d, cid, Mt, stat, k, kp, dist, out); \
-        else                                                                                                       \
-            hipLaunchKernelGGL((evalcluster_rows_csr_kernel<NB, U, int32_t>), g, b, 0, st, crow,                   \
-                               reinterpret_cast<const int32_t*>(col), val, n, d, cid, Mt, stat, k, kp, dist, out); \
-    } while (0)
-    if (kp == 64) ALINK_EV_CSR(1, 8);
-    else if (kp == 128) ALINK_EV_CSR(2, 8);
-    else ALINK_EV_CSR(4, 4);
-#undef ALINK_EV_CSR
+    ALINK_CSR_LAUNCH(evalcluster_rows_csr_kernel, kp, idx64, csr::wave_blocks(n, grid, csr::WAVES, csr::WAVE_GRID), st,
+                     crow, col, val, n, d, cid, Mt, stat, k, kp, dist, out);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

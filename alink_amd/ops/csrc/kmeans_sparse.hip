@@ -1,14 +1,12 @@
 // Sparse-vector KMeans (``ops/kmeans_sparse.py``): CSR rows against dense centroids, all arithmetic fp64.
 //
-// * alink_kmeans_sparse_nearest — one wave per CSR row.  The centroids come transposed and padded, Ct [d, kp] with
-//   kp a multiple of 64, so a stored entry (j, v) reads the contiguous kp-double row Ct[j, :]: lane l owns the
-//   clusters l, l + 64, ... of a block of up to 256 clusters in registers and does acc += v * Ct[j*kp + c].  The
-//   wave loads 64 entries at a time (coalesced) and walks them with wave-uniform broadcasts, several entries'
-//   gathers in flight.  score_c = cn[c] - mul * dot_c (EUCLIDEAN: cn = |c|^2, mul = 2; COSINE: cn = 0, mul = 1;
-//   padded clusters carry cn = +inf), the wave argmin keeps the LOWEST index on equal scores (the reference's
-//   strict `<` scan).  k beyond one register block loops over cluster blocks with a running best.  Entries whose
-//   column is outside [0, d) contribute nothing, to the dot products and to |x|^2 alike: the guard replaces them
-//   by (column 0, value 0) before any address is formed.
+// * alink_kmeans_sparse_nearest — one wave per CSR row, on the row walk of csr_rows.h (the table is the centroids,
+//   transposed and padded, Ct [d, kp]; the lane / cluster map and the entry guard are described there): per cluster
+//   block the walk gives the lane's dots and |x|^2, and this file keeps the score and the argmin.
+//   score_c = cn[c] - mul * dot_c (EUCLIDEAN: cn = |c|^2, mul = 2; COSINE: cn = 0, mul = 1; padded clusters carry
+//   cn = +inf), the wave argmin keeps the LOWEST index on equal scores (the reference's strict `<` scan).  k beyond
+//   one register block loops over cluster blocks with a running best.  Entries whose column is outside [0, d)
+//   contribute nothing, to the dot products and to |x|^2 alike.
 //   Outputs (each optional): idx int32 [n]; best distance fp64 [n] (EUCLIDEAN max(0, |x|^2 + score), COSINE
 //   1 + score); exact per-cluster int64 counts by integer atomics (the k-means|| weights pass).
 // * alink_kmeans_sparse_accum — per-cluster column sums without float atomics, through the CSC view of the rows
@@ -18,78 +16,34 @@
 //   order in registers.  A single-chunk column's sums go straight to sumT [d, kp]; a longer column's chunk
 //   partials go to a side buffer that alink_kmeans_sparse_accum (second launch) adds in chunk order.  The result
 //   does not depend on the grid and is bitwise identical from run to run.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "lane_bcast.h"
+#include "csr_rows.h"
 
 namespace {
 
-using lane::bcast_f64;
-using lane::bcast_i64;
+using csr::NBMAX;
+using csr::WAVES;
 
-constexpr int SP_WAVES = 4;        // waves (rows / work items) per 256-thread workgroup
-constexpr int SP_NB = 4;           // cluster blocks of 64 a lane holds at most (256 clusters per pass)
-
-// NB: cluster blocks of 64 per pass (kp >= 64 * NB unless NB == SP_NB, where the tail block is guarded);
-// U: entries whose gathers are issued together.
+// NB, U: cluster blocks of 64 per pass and entries whose gathers are issued together (csr_rows.h).
 template <int NB, int U, typename I>
-__global__ __launch_bounds__(64 * SP_WAVES) void sparse_nearest_kernel(
+__global__ __launch_bounds__(64 * WAVES) void sparse_nearest_kernel(
         const int64_t* __restrict__ crow, const I* __restrict__ col, const double* __restrict__ val, int64_t n,
         int64_t d, const double* __restrict__ Ct, const double* __restrict__ cn, int kp, double mul, int cosine,
         int* __restrict__ idx_out, double* __restrict__ dist_out, unsigned long long* __restrict__ counts) {
     const int lane = threadIdx.x & 63;
-    const int64_t w0 = (int64_t)blockIdx.x * SP_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t nw = (int64_t)gridDim.x * SP_WAVES;
-    for (int64_t r = w0; r < n; r += nw) {
+    const int64_t nw = csr::item_stride();
+    for (int64_t r = csr::first_item(); r < n; r += nw) {
         const int64_t s = crow[r], e = crow[r + 1];
         double best = __builtin_inf();
         int besti = 0;
         double xn = 0.0;
         for (int cb = 0; cb < kp; cb += 64 * NB) {
-            double acc[NB];
-#pragma unroll
-            for (int b = 0; b < NB; ++b) acc[b] = 0.0;
-            xn = 0.0;
-            for (int64_t p = s; p < e; p += 64) {
-                const int m = (int)((e - p) < 64 ? (e - p) : 64);
-                // guarded entry of this lane: an out-of-range column (or a lane past the row) becomes (0, 0.0)
-                int64_t cj = 0;
-                double vj = 0.0;
-                if (lane < m) {
-                    const int64_t c = (int64_t)col[p + lane];
-                    if (c >= 0 && c < d) {
-                        cj = c;
-                        vj = val[p + lane];
-                    }
-                }
-                for (int j0 = 0; j0 < m; j0 += U) {
-                    double v[U];
-                    double t[U][NB];
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        // lanes j0 + u >= m hold (0, 0.0): they read row 0 of Ct and add nothing
-                        const int j = (j0 + u) & 63;
-                        const int64_t c = bcast_i64(cj, j);
-                        v[u] = bcast_f64(vj, j);
-                        const double* __restrict__ rowp = Ct + c * (int64_t)kp + cb + lane;
-#pragma unroll
-                        for (int b = 0; b < NB; ++b)
-                            t[u][b] = (NB < SP_NB || cb + 64 * b < kp) ? rowp[64 * b] : 0.0;
-                    }
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        xn = fma(v[u], v[u], xn);
-#pragma unroll
-                        for (int b = 0; b < NB; ++b) acc[b] = fma(v[u], t[u][b], acc[b]);
-                    }
-                }
-            }
+            const auto w = csr::row_dots<NB, U, NBMAX>(col, val, s, e, d, Ct, kp, cb, lane);
+            xn = w.xn;
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
                 const int c = cb + 64 * b + lane;
-                if (NB < SP_NB || cb + 64 * b < kp) {
-                    const double sc = cn[c] - mul * acc[b];
+                if (NB < NBMAX || cb + 64 * b < kp) {
+                    const double sc = cn[c] - mul * w.acc[b];
                     if (sc < best) {          // ascending c within a lane: strict < keeps the lowest index
                         best = sc;
                         besti = c;
@@ -121,14 +75,14 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sparse_nearest_kernel(
 // One wave per work item w: entries [wstart[w], wstart[w] + wlen[w]) of the CSC arrays, all of column wcol[w].
 // The sums of clusters [cb, cb + 64 NB) go to sumT[wcol[w], :] (wslot[w] < 0) or part[wslot[w], :].
 template <int NB>
-__global__ __launch_bounds__(64 * SP_WAVES) void sparse_accum_kernel(
+__global__ __launch_bounds__(64 * WAVES) void sparse_accum_kernel(
         const int32_t* __restrict__ rows, const double* __restrict__ vals, const int* __restrict__ idx,
         int64_t nwork, const int64_t* __restrict__ wcol, const int64_t* __restrict__ wstart,
         const int32_t* __restrict__ wlen, const int64_t* __restrict__ wslot, int kp, double* __restrict__ sumT,
         double* __restrict__ part) {
     const int lane = threadIdx.x & 63;
-    const int64_t w0 = (int64_t)blockIdx.x * SP_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t nw = (int64_t)gridDim.x * SP_WAVES;
+    const int64_t w0 = (int64_t)blockIdx.x * WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nw = (int64_t)gridDim.x * WAVES;
     for (int64_t w = w0; w < nwork; w += nw) {
         const int64_t s = wstart[w];
         const int len = wlen[w];
@@ -148,26 +102,26 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sparse_accum_kernel(
                 }
                 for (int j = 0; j < m; ++j) {
                     const int mine = __builtin_amdgcn_readlane(a, j) - lane;     // 64 b on the owning lane
-                    const double vj = bcast_f64(v, j);
+                    const double vj = lane::bcast_f64(v, j);
 #pragma unroll
                     for (int b = 0; b < NB; ++b) acc[b] += (mine == 64 * b) ? vj : 0.0;
                 }
             }
 #pragma unroll
             for (int b = 0; b < NB; ++b)
-                if (NB < SP_NB || cb + 64 * b < kp) dst[cb + 64 * b + lane] = acc[b];
+                if (NB < NBMAX || cb + 64 * b < kp) dst[cb + 64 * b + lane] = acc[b];
         }
     }
 }
 
 // The columns that span several chunks: sumT[mcol[i], :] = part[mfirst[i]] + part[mfirst[i] + 1] + ... in chunk
 // order, one wave per column, one lane per cluster.
-__global__ __launch_bounds__(64 * SP_WAVES) void sparse_accum_merge_kernel(
+__global__ __launch_bounds__(64 * WAVES) void sparse_accum_merge_kernel(
         int64_t nmulti, const int64_t* __restrict__ mcol, const int64_t* __restrict__ mfirst,
         const int64_t* __restrict__ mcount, int kp, const double* __restrict__ part, double* __restrict__ sumT) {
     const int lane = threadIdx.x & 63;
-    const int64_t w0 = (int64_t)blockIdx.x * SP_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t nw = (int64_t)gridDim.x * SP_WAVES;
+    const int64_t w0 = (int64_t)blockIdx.x * WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t nw = (int64_t)gridDim.x * WAVES;
     for (int64_t i = w0; i < nmulti; i += nw) {
         const int64_t f = mfirst[i], cnt = mcount[i];
         double* __restrict__ dst = sumT + mcol[i] * (int64_t)kp;
@@ -177,13 +131,6 @@ __global__ __launch_bounds__(64 * SP_WAVES) void sparse_accum_merge_kernel(
             dst[c] = a;
         }
     }
-}
-
-inline int grid_for(int64_t items, int grid) {
-    int64_t blocks = (items + SP_WAVES - 1) / SP_WAVES;
-    const int64_t cap = grid > 0 ? grid : 16384;
-    if (blocks > cap) blocks = cap;
-    return (int)(blocks < 1 ? 1 : blocks);
 }
 
 }  // namespace
@@ -199,23 +146,8 @@ int alink_kmeans_sparse_nearest(const int64_t* crow, const void* col, int idx64,
     if (n <= 0) return 0;
     if (d < 1 || kp < 64 || kp % 64 != 0) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 g(grid_for(n, grid)), b(64 * SP_WAVES);
-    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
-#define ALINK_SP_NEAREST(NB, U)                                                                                    \
-    do {                                                                                                           \
-        if (idx64)                                                                                                 \
-            hipLaunchKernelGGL((sparse_nearest_kernel<NB, U, int64_t>), g, b, 0, st, crow,                         \
-                               reinterpret_cast<const int64_t*>(col), val, n, d, Ct, cn, kp, mul, cosine, idx,     \
-                               dist, cnt);                                                                         \
-        else                                                                                                       \
-            hipLaunchKernelGGL((sparse_nearest_kernel<NB, U, int32_t>), g, b, 0, st, crow,                         \
-                               reinterpret_cast<const int32_t*>(col), val, n, d, Ct, cn, kp, mul, cosine, idx,     \
-                               dist, cnt);                                                                         \
-    } while (0)
-    if (kp == 64) ALINK_SP_NEAREST(1, 8);
-    else if (kp == 128) ALINK_SP_NEAREST(2, 8);
-    else ALINK_SP_NEAREST(4, 4);
-#undef ALINK_SP_NEAREST
+    ALINK_CSR_LAUNCH(sparse_nearest_kernel, kp, idx64, csr::wave_blocks(n, grid, WAVES, csr::WAVE_GRID), st, crow, col,
+                     val, n, d, Ct, cn, kp, mul, cosine, idx, dist, reinterpret_cast<unsigned long long*>(counts));
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -230,7 +162,7 @@ int alink_kmeans_sparse_accum(const int32_t* rows, const double* vals, const int
     if (nwork <= 0) return 0;
     if (kp < 64 || kp % 64 != 0) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 g(grid_for(nwork, grid)), b(64 * SP_WAVES);
+    const dim3 g(csr::wave_blocks(nwork, grid, WAVES, csr::WAVE_GRID)), b(64 * WAVES);
     if (kp == 64)
         hipLaunchKernelGGL((sparse_accum_kernel<1>), g, b, 0, st, rows, vals, idx, nwork, wcol, wstart, wlen, wslot,
                            kp, sumT, part);
@@ -241,8 +173,8 @@ int alink_kmeans_sparse_accum(const int32_t* rows, const double* vals, const int
         hipLaunchKernelGGL((sparse_accum_kernel<4>), g, b, 0, st, rows, vals, idx, nwork, wcol, wstart, wlen, wslot,
                            kp, sumT, part);
     if (nmulti > 0)
-        hipLaunchKernelGGL(sparse_accum_merge_kernel, dim3(grid_for(nmulti, grid)), b, 0, st, nmulti, mcol, mfirst,
-                           mcount, kp, part, sumT);
+        hipLaunchKernelGGL(sparse_accum_merge_kernel, dim3(csr::wave_blocks(nmulti, grid, WAVES, csr::WAVE_GRID)), b, 0,
+                           st, nmulti, mcol, mfirst, mcount, kp, part, sumT);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

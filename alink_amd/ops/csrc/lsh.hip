@@ -29,7 +29,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lane_bcast.h"
+
 namespace {
+
+using lane::group_sum;
+using lane::group_sum_int;
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
 
@@ -135,22 +140,6 @@ __global__ __launch_bounds__(LSH_THREADS) void lsh_brp_kernel(
         }
         out[i] = (int)mm_fin(h, P);
     }
-}
-
-// the sum of the G lanes' values (G a power of two, groups aligned to G): both partners of a step add the same two
-// values, so every lane of the group ends with the same bits
-template <int G>
-__device__ __forceinline__ double group_sum(double a) {
-#pragma unroll
-    for (int o = 1; o < G; o <<= 1) a += __shfl_xor(a, o, 64);
-    return a;
-}
-
-template <int G>
-__device__ __forceinline__ int group_sum_int(int a) {
-#pragma unroll
-    for (int o = 1; o < G; o <<= 1) a += __shfl_xor(a, o, 64);
-    return a;
 }
 
 // the position of key in the strictly ascending col[beg .. beg + len), or -1

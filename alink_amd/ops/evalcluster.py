@@ -14,7 +14,8 @@ row pass and the per-cluster sums of its output, on the row kinds of ``ops/kmean
 A row whose ``cid`` is outside ``[0, k)`` adds nothing to any sum and gets a zero row in the block.
 
 GPU: ``csrc/evalcluster.hip`` — fp64 rows (1 <= d <= 1024) on the fp64 matrix cores with the means staged in LDS,
-CSR rows one wave per row against the transposed mean table; the sums through the sort-based dense accumulate and the
+CSR rows one wave per row against the transposed mean table (the row walk of ``csrc/csr_rows.h``, handed over by
+``ops/csr.py``); the sums through the sort-based dense accumulate and the
 CSC accumulate, no float atomics: bitwise identical from run to run and for every grid.
 Every other kind (CPU rows, fp32 rows, wider dense rows, an empty partition): the torch functions below, chunked
 over rows; CSR rows never become a dense matrix.  Non-finite rows are not guaranteed to agree between the two.
@@ -25,7 +26,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib, kmeans_dense64 as kd64, kmeans_rows as krows, kmeans_sparse as ksp
+from . import _lib, csr, kmeans_dense64 as kd64, kmeans_rows as krows
 
 __all__ = ["DIST_CODES", "eval_rows", "sorted_work", "cluster_sums", "row_pass", "cluster_row_sums", "distance",
            "row_pass_torch"]
@@ -65,7 +66,7 @@ def _hip_kind(rows, k: int):
     if isinstance(rows, krows._Dense64Rows):
         return "f64" if kd64.use_hip(rows.X, k) else None
     if isinstance(rows, krows._SparseRows):
-        return "csr" if ksp.use_hip(rows.X) else None
+        return "csr" if csr.use_hip(rows.X) else None
     return None
 
 
@@ -143,7 +144,7 @@ def _row_pass_csr_torch(fm, d: int, cid, mean, cnt, n2, code: int) -> torch.Tens
     n, k = fm.nrows, mean.shape[0]
     dev = fm.val.device
     out = torch.zeros((n, 3), dtype=torch.float64, device=dev)
-    col, val = ksp.clipped(fm, d)                  # entries outside [0, d) are (0, 0.0): they add nothing
+    col, val = csr.clipped(fm, d)                  # entries outside [0, d) are (0, 0.0): they add nothing
     safe = krows.sparse_view(fm, d, val.to(torch.float64))
     safe.col = col
     Mt = mean.t().contiguous()
@@ -218,17 +219,13 @@ def _row_pass_csr(fm, d: int, cid, mean, cnt, n2, code: int, grid: int) -> torch
     dev = fm.val.device
     n = fm.nrows
     k = mean.shape[0]
-    kp = ksp.kp(k)
-    Mt = torch.zeros((d, kp), dtype=torch.float64, device=dev)
-    Mt[:, :k] = mean.t()
+    kp = csr.kp(k)
+    Mt = csr.padded_transpose(mean, kp)
     stat = _cluster_records(kp, mean, cnt, n2)
-    crow, col, val = fm.crow.contiguous(), fm.col.contiguous(), fm.val.contiguous()
-    if int(crow.numel()) != n + 1 or col.numel() != val.numel():
-        raise ValueError("malformed CSR matrix")
+    alive, head = csr.row_args(fm, d)      # alive: the arrays behind head's pointers
     out = torch.empty((n, 3), dtype=torch.float64, device=dev)
-    _lib.call("alink_evalcluster_rows_csr", crow.data_ptr(), col.data_ptr(), int(col.dtype == torch.int64),
-              val.data_ptr(), n, d, cid.data_ptr(), Mt.data_ptr(), stat.data_ptr(), k, kp, code, out.data_ptr(),
-              int(grid), _lib.stream_ptr(dev))
+    _lib.call("alink_evalcluster_rows_csr", *head, cid.data_ptr(), Mt.data_ptr(), stat.data_ptr(), k, kp, code,
+              out.data_ptr(), int(grid), _lib.stream_ptr(dev))
     return out
 
 

@@ -26,7 +26,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib, bisecting as bops, kmeans as kops, kmeans_dense64 as kd64, kmeans_sparse as ksp
+from . import _lib, bisecting as bops, csr, kmeans as kops, kmeans_dense64 as kd64, kmeans_sparse as ksp
 from .kmeans_sparse import sparse_selected  # noqa: F401  (the selection rule of sparse columns, for the callers)
 
 __all__ = ["rows", "Rows", "column_kind", "sparse_selected", "sparse_rows", "pairwise_distance"]
@@ -181,7 +181,7 @@ class _SparseRows(Rows):
     def _dot_chunks(self, C: torch.Tensor):
         """Yields (first row, ``X[s:e] @ C.T`` fp64 [m, k]) in row chunks of the CSR product."""
         fm, d = self.X, self.d
-        col, val = ksp.clipped(fm, d)
+        col, val = csr.clipped(fm, d)
         safe = sparse_view(fm, d, val)
         safe.col = col
         Ct = C.t().contiguous()
@@ -203,7 +203,7 @@ class _SparseRows(Rows):
         return ksp.row_sqnorm(self.X, self.d)
 
     def _descend(self, table, slot, levels, grid):
-        if ksp.use_hip(self.X):
+        if csr.use_hip(self.X):
             return bops.descend_csr(self.X, table, slot, levels, grid)
         return _torch_descend(lambda M: torch.cat([dot for _, dot in self._dot_chunks(M)]), table, slot, levels)
 
@@ -212,7 +212,7 @@ class _SparseRows(Rows):
         buf = torch.zeros((nslots, d + 2), dtype=torch.float64, device=fm.device)
         idx = torch.where((slot >= 0) & (slot < nslots), slot, torch.full_like(slot, -1)).to(torch.int32)
         counts = torch.bincount(idx.to(torch.int64) + 1, minlength=nslots + 1)[1:]
-        if ksp.use_hip(fm):
+        if csr.use_hip(fm):
             buf[:, :d + 1] = ksp.accumulate_hip(fm, idx.contiguous(), nslots, d, counts, grid)
             if sqnorm:      # the per-row norms through the dense accumulate at d = 1: no float atomics here either
                 sq = self.row_sqnorm()[:, None]

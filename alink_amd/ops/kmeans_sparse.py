@@ -12,9 +12,10 @@ stored entries into the dense sum matrix, ``FastDistance`` takes sparse samples 
 * ``prepare(fm)``: the CSC view of the rows (a stable sort of the entries by column, built once per training run
   and cached on the matrix) with its (column, chunk) work list.
 
-GPU: ``csrc/kmeans_sparse.hip`` — one wave per row for the assignment (a gather of the transposed, padded
-centroid table), one wave per (column, chunk of ``ACCUM_CHUNK`` entries) for the sums, no float atomics: the sums
-are bitwise identical from run to run and for every grid.  Entries whose column is outside ``[0, d)`` are ignored.
+GPU: ``csrc/kmeans_sparse.hip`` — one wave per row for the assignment (the CSR row walk of ``csrc/csr_rows.h``
+against the transposed, padded centroid table), one wave per (column, chunk of ``ACCUM_CHUNK`` entries) for the sums,
+no float atomics: the sums are bitwise identical from run to run and for every grid.  Entries whose column is outside
+``[0, d)`` are ignored.  Which matrices go to the kernels and how their arrays are handed over: ``ops/csr.py``.
 CPU (and the oracle of the tests): ``nearest_torch`` / ``assign_accumulate_torch``, chunked over rows.
 
 With a GPU present a missing kernel library raises, unless ``ALINK_ALLOW_TORCH_FALLBACK=1``.
@@ -26,12 +27,11 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, csr
 
 __all__ = ["ACCUM_CHUNK", "sparse_supported", "sparse_selected", "prepare", "nearest", "nearest_counts",
            "assign_accumulate", "nearest_torch", "assign_accumulate_torch", "row_sqnorm", "take_dense",
-           # shared with ops/evalcluster.py and ops/kmeans_rows.py
-           "use_hip", "clipped", "kp", "accumulate_torch", "nearest_hip"]
+           "accumulate_torch", "nearest_hip"]
 
 ACCUM_CHUNK = 512       # entries of one column that one wave sums; longer columns are split and merged in order
 DENSE_DMAX = 1024       # the largest d a dense HIP KMeans kernel covers (ops/kmeans.py): sparse input wider than
@@ -53,21 +53,7 @@ def sparse_selected(column_is_sparse: bool, vector_size: int) -> bool:
     return int(vector_size) > DENSE_DMAX
 
 
-def sparse_supported(fm) -> bool:
-    """Whether the HIP kernels take this matrix: a sparse fp64 FeatureMatrix on a GPU with int32 / int64 columns."""
-    return (not isinstance(fm, torch.Tensor) and getattr(fm, "dense", 0) is None and fm.val.is_cuda
-            and fm.val.dtype == torch.float64 and fm.col.dtype in (torch.int32, torch.int64)
-            and fm.nrows < 2 ** 31)
-
-
-def use_hip(fm) -> bool:
-    """Whether this matrix goes to the HIP CSR kernels: False on the CPU, an error for a GPU matrix the kernels do
-    not take, else whether the kernel library is enabled."""
-    if not fm.val.is_cuda:
-        return False
-    if not sparse_supported(fm):
-        raise ValueError("sparse KMeans on the GPU needs fp64 values, int32/int64 columns and fewer than 2^31 rows")
-    return _lib.kernels_enabled()
+sparse_supported = csr.supported    # whether the HIP kernels take a matrix, under the name the tests ask by
 
 
 def _dist_code(dist_type: str) -> int:
@@ -80,13 +66,6 @@ def _dist_code(dist_type: str) -> int:
 # ---------------------------------------------------------------------------------------------------
 # torch path (CPU, oracle)
 # ---------------------------------------------------------------------------------------------------
-def clipped(fm, d: int):
-    """(col int64, val) with the entries outside [0, d) turned into (0, 0.0): they then add nothing."""
-    col = fm.col.to(torch.int64)
-    ok = (col >= 0) & (col < d)
-    return torch.where(ok, col, torch.zeros_like(col)), torch.where(ok, fm.val, torch.zeros_like(fm.val))
-
-
 def row_sqnorm(fm, d: Optional[int] = None) -> torch.Tensor:
     """|x|^2 per row over the entries inside [0, d), summed in entry order (on the GPU by the CSR mat-vec kernel,
     which has a fixed order; ``index_add_`` there would sum by atomics)."""
@@ -95,7 +74,7 @@ def row_sqnorm(fm, d: Optional[int] = None) -> torch.Tensor:
     out = torch.zeros(n, dtype=torch.float64, device=fm.val.device)
     if n == 0 or fm.val.numel() == 0 or d == 0:
         return out
-    col, val = clipped(fm, d)
+    col, val = csr.clipped(fm, d)
     if val.is_cuda and _lib.available():
         from .feature import csr_mv
         return csr_mv(fm.crow, col, val * val, torch.ones(d, dtype=torch.float64, device=val.device))
@@ -134,7 +113,7 @@ def _scores_torch(fm, C: torch.Tensor, cosine: int, chunk: int):
     Cd = C.to(device=fm.val.device, dtype=torch.float64)
     Ct = Cd.t().contiguous()
     cn = (Cd * Cd).sum(1)
-    col, val = clipped(fm, d)
+    col, val = csr.clipped(fm, d)
     counts = fm.crow[1:] - fm.crow[:-1]
     n = fm.nrows
     for s in range(0, n, chunk):
@@ -173,7 +152,7 @@ def accumulate_torch(fm, idx: torch.Tensor, k: int, d: int) -> torch.Tensor:
         return buf
     buf[:, d] = torch.bincount(idx, minlength=k).to(torch.float64)
     if fm.val.numel():
-        col, val = clipped(fm, d)
+        col, val = csr.clipped(fm, d)
         buf.view(-1).index_add_(0, idx[fm.row_ids()] * (d + 1) + col, val.to(torch.float64))
     return buf
 
@@ -188,28 +167,10 @@ def assign_accumulate_torch(fm, C: torch.Tensor, dist_type: str, chunk: int = TO
 # ---------------------------------------------------------------------------------------------------
 # HIP path
 # ---------------------------------------------------------------------------------------------------
-def kp(k: int) -> int:
-    """k padded to the cluster blocks of the CSR kernels: a multiple of 64, at least 64 (the ``kp`` of
-    ``csrc/kmeans_sparse.hip`` and ``csrc/evalcluster.hip``)."""
-    return max(64, (int(k) + 63) // 64 * 64)
-
-
-def _centroid_operands(C: torch.Tensor, cosine: int, dev):
-    """Ct [d, kp] fp64 (transposed, zero-padded) and the score offsets cn [kp] (+inf on the padded clusters)."""
-    k, d = C.shape
-    kpad = kp(k)
-    Cd = C.to(device=dev, dtype=torch.float64)
-    Ct = torch.zeros((d, kpad), dtype=torch.float64, device=dev)
-    Ct[:, :k] = Cd.t()
-    cn = torch.full((kpad,), float("inf"), dtype=torch.float64, device=dev)
-    cn[:k] = 0.0 if cosine else (Cd * Cd).sum(1)
-    return Ct, cn, kpad
-
-
 def nearest_hip(fm, C: torch.Tensor, dist_type: str, want_idx: bool, want_dist: bool, want_counts: bool,
                  grid: int = 0):
     """``alink_kmeans_sparse_nearest`` with the outputs the caller asks for: (idx int32 [n], dist fp64 [n],
-    counts int64 [kp(k)]), each None unless wanted.  Nothing is launched for an empty matrix."""
+    counts int64 [csr.kp(k)]), each None unless wanted.  Nothing is launched for an empty matrix."""
     global SPARSE_CALLS
     cosine = _dist_code(dist_type)
     dev = fm.val.device
@@ -217,21 +178,19 @@ def nearest_hip(fm, C: torch.Tensor, dist_type: str, want_idx: bool, want_dist: 
     n = fm.nrows
     idx = torch.zeros(n, dtype=torch.int32, device=dev) if want_idx else None
     dist = torch.zeros(n, dtype=torch.float64, device=dev) if want_dist else None
-    kpad = kp(k)
+    kpad = csr.kp(k)
     counts = torch.zeros(kpad, dtype=torch.int64, device=dev) if want_counts else None
     if n == 0:      # nothing is launched for an empty partition
         return idx, dist, counts
     if k < 1 or d < 1:
         raise ValueError("sparse KMeans needs at least one centroid and one column")
-    Ct, cn, kpad = _centroid_operands(C, cosine, dev)
-    crow = fm.crow.contiguous()
-    col = fm.col.contiguous()
-    val = fm.val.contiguous()
-    if int(crow.numel()) != n + 1 or col.numel() != val.numel():
-        raise ValueError("malformed CSR matrix")
-    _lib.call("alink_kmeans_sparse_nearest", crow.data_ptr(), col.data_ptr(), int(col.dtype == torch.int64),
-              val.data_ptr(), n, d, Ct.data_ptr(), cn.data_ptr(), kpad, 1.0 if cosine else 2.0, cosine,
-              idx.data_ptr() if want_idx else None, dist.data_ptr() if want_dist else None,
+    Cd = C.to(device=dev, dtype=torch.float64)
+    Ct = csr.padded_transpose(Cd, kpad)
+    cn = torch.full((kpad,), float("inf"), dtype=torch.float64, device=dev)     # +inf on the padded clusters
+    cn[:k] = 0.0 if cosine else (Cd * Cd).sum(1)
+    alive, head = csr.row_args(fm, d)      # alive: the arrays behind head's pointers
+    _lib.call("alink_kmeans_sparse_nearest", *head, Ct.data_ptr(), cn.data_ptr(), kpad, 1.0 if cosine else 2.0,
+              cosine, idx.data_ptr() if want_idx else None, dist.data_ptr() if want_dist else None,
               counts.data_ptr() if want_counts else None, int(grid), _lib.stream_ptr(dev))
     SPARSE_CALLS += 1
     return idx, dist, counts
@@ -240,7 +199,7 @@ def nearest_hip(fm, C: torch.Tensor, dist_type: str, want_idx: bool, want_dist: 
 def nearest(fm, C: torch.Tensor, dist_type: str, grid: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """Nearest centroid per row: (idx int64 [n], dist fp64 [n]) — squared distance for EUCLIDEAN, ``1 - x.c`` for
     COSINE.  Equal scores go to the lowest centroid index; an empty row takes ``argmin |c|^2``."""
-    if use_hip(fm):
+    if csr.use_hip(fm):
         idx, dist, _ = nearest_hip(fm, C, dist_type, True, True, False, grid)
         return idx.to(torch.int64), dist
     return nearest_torch(fm, C, dist_type)
@@ -249,7 +208,7 @@ def nearest(fm, C: torch.Tensor, dist_type: str, grid: int = 0) -> Tuple[torch.T
 def nearest_counts(fm, C: torch.Tensor, dist_type: str, grid: int = 0) -> torch.Tensor:
     """Rows per nearest centroid, exact int64 [k] (integer atomics on the GPU, no per-row output)."""
     k = C.shape[0]
-    if use_hip(fm):
+    if csr.use_hip(fm):
         return nearest_hip(fm, C, dist_type, False, False, True, grid)[2][:k]
     return torch.bincount(nearest_torch(fm, C, dist_type)[0], minlength=k)
 
@@ -320,7 +279,7 @@ def accumulate_hip(fm, idx: torch.Tensor, k: int, d: int, counts: Optional[torch
     csc = prepare(fm, d)
     if csc.nwork == 0:
         return buf
-    kpad = kp(k)
+    kpad = csr.kp(k)
     sumT = torch.zeros((d, kpad), dtype=torch.float64, device=dev)
     part = torch.empty((max(csc.nslots, 1), kpad), dtype=torch.float64, device=dev)
     _lib.call("alink_kmeans_sparse_accum", csc.rows.data_ptr(), csc.vals.data_ptr(), idx.data_ptr(), csc.nwork,
@@ -335,7 +294,7 @@ def accumulate_hip(fm, idx: torch.Tensor, k: int, d: int, counts: Optional[torch
 def assign_accumulate(fm, C: torch.Tensor, dist_type: str, grid: int = 0) -> torch.Tensor:
     """The Lloyd step's ``[k, d+1]`` fp64 buffer ``[sum_x | count]`` for this rank's sparse rows."""
     k, d = C.shape
-    if use_hip(fm):
+    if csr.use_hip(fm):
         idx, _, counts = nearest_hip(fm, C, dist_type, True, False, True, grid)
         return accumulate_hip(fm, idx, k, d, counts, grid)
     return assign_accumulate_torch(fm, C, dist_type)

@@ -99,10 +99,11 @@ def _wide_mean(case):
 
 
 @pytest.mark.parametrize("idx_dtype", [torch.int32, torch.int64])
-@pytest.mark.parametrize("k", [1, 64, 65, 300])
+@pytest.mark.parametrize("k", [1, 64, 65, 129, 256, 300])
 def test_csr_row_pass_equals_numpy(k, idx_dtype):
     """d = 2^18, empty rows, rows of 1 .. 130 entries in random stored order, entries outside [0, d) (-1, d,
-    d + 7) that must add nothing; one, two and (k = 300) five cluster blocks of 64."""
+    d + 7) that must add nothing; one, two, three (k = 129: the tail guard in the first pass of four blocks), four
+    (k = 256: an exactly full pass) and (k = 300) five cluster blocks of 64."""
     from alink_amd.ops import evalcluster as ev
     for dist in DISTS:
         case = H.csr_case(k, dist)

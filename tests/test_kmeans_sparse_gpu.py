@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 EPS = 2.0 ** -53
 N, D = 1003, 1500               # 1003 rows: not a multiple of the 4 waves of a workgroup
 ROW_LENS = (0, 1, 63, 64, 65, 200)
-KS = (1, 3, 64, 65, 100, 300)
+KS = (1, 3, 64, 65, 100, 129, 256, 300)
 
 
 def _fm(crow, col, val, d, device, col_dtype=torch.int64):
