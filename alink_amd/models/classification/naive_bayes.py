@@ -8,6 +8,11 @@ softmax of the log scores).
 
 Device path: the per-label sums are one ``Y^T X`` product (one-hot(label) * weight against the dense or CSR
 sample matrix) followed by a single all-reduce; prediction is one ``X theta^T`` GEMM per micro-batch.
+
+From ``ops.naive_bayes.NB_MIN_ROWS`` rows of a GPU partition on (``ALINK_NB_HIP``, docs/flags.md), sparse fp64 columns
+and dense fp64 columns of at most 1024 dims take ``ops/naive_bayes.py`` instead: the sums through the exact
+accumulate kernels, the scores, the first strict maximum and the softmax in one HIP row kernel, the detail strings
+through the batched formatter.  The log formulas and the model rows stay on the host.
 """
 from __future__ import annotations
 
@@ -25,9 +30,10 @@ from ...common.model.converter import LabeledModelDataConverter
 from ...common.params import Params
 from ...common.table import Column, MTable
 from ...common.types import Types
+from ...ops import _lib, naive_bayes as nbops
 from ...parallel import comm
 from ..common.features import FeatureMatrix, extract_features, global_vector_size
-from ..linear.model import _dev, _recover_label, label_column
+from ..linear.model import _detail_json, _dev, _recover_label, label_column
 
 
 def _recount_crow(crow: torch.Tensor, keep: torch.Tensor) -> torch.Tensor:
@@ -37,6 +43,12 @@ def _recount_crow(crow: torch.Tensor, keep: torch.Tensor) -> torch.Tensor:
     return c[crow.to(torch.int64)]
 
 __all__ = ["train_naive_bayes_text", "NaiveBayesTextModelDataConverter", "NaiveBayesTextModelMapper"]
+
+
+def _device_path(fm, device, n_rows: int) -> bool:
+    """Whether a partition of ``n_rows`` rows takes the kernels of ``ops/naive_bayes.py``: a column they take, on a
+    GPU, from ``NB_MIN_ROWS`` rows on (``ALINK_NB_HIP=1``: always, ``=0``: never)."""
+    return nbops.supported(fm) and _lib.sized_gate("ALINK_NB_HIP", device, n_rows, nbops.NB_MIN_ROWS)
 
 
 def _pget(p: Params, name, default=None):
@@ -97,14 +109,20 @@ def train_naive_bayes_text(mt: MTable, params: Params, env):
     L = len(keys)
     pos = {k: i for i, k in enumerate(keys)}
     y = torch.tensor([pos[java_str(v)] for v in labels_local], dtype=torch.long, device=dev)
-    w = torch.ones(len(labels_local), dtype=torch.float64, device=dev) if wcol is None else \
-        torch.tensor([float(x) for x in mt.column_values(wcol)], dtype=torch.float64, device=dev)
-    Y = torch.zeros((len(labels_local), L), dtype=torch.float64, device=dev)
-    if len(labels_local):
-        Y[torch.arange(len(labels_local), device=dev), y] = w
-    feat = fm.rmm(Y, d).T.contiguous() if len(labels_local) else torch.zeros((L, d), dtype=torch.float64,
-                                                                                device=dev)
-    wsum = Y.sum(0)
+    if len(labels_local) and _device_path(fm, fm.device, len(labels_local)):
+        # per-label sums without the [n, L] one-hot and the [nnz, L] product (ops/naive_bayes.py)
+        w = None if wcol is None else \
+            torch.tensor([float(x) for x in mt.column_values(wcol)], dtype=torch.float64, device=dev)
+        feat, wsum = nbops.label_sums(nbops.train_rows(fm, d, w), y, w, L)
+    else:
+        w = torch.ones(len(labels_local), dtype=torch.float64, device=dev) if wcol is None else \
+            torch.tensor([float(x) for x in mt.column_values(wcol)], dtype=torch.float64, device=dev)
+        Y = torch.zeros((len(labels_local), L), dtype=torch.float64, device=dev)
+        if len(labels_local):
+            Y[torch.arange(len(labels_local), device=dev), y] = w
+        feat = fm.rmm(Y, d).T.contiguous() if len(labels_local) else torch.zeros((L, d), dtype=torch.float64,
+                                                                                    device=dev)
+        wsum = Y.sum(0)
     buf = torch.cat([feat.reshape(-1), wsum])
     comm.all_reduce(buf, "sum")
     feat, wsum = buf[:L * d].reshape(L, d).cpu().numpy(), buf[L * d:].cpu().numpy()
@@ -120,10 +138,23 @@ def train_naive_bayes_text(mt: MTable, params: Params, env):
             "vectorCol": vec_col}
 
 
+def _label_or_null(labels, idx, ok, t) -> Column:
+    """``labels[idx]`` as a column of type ``t``, null where ``ok`` is False (a row with no score above -inf)."""
+    if ok.all():
+        return label_column(labels, idx, t)
+    lab = np.empty(len(labels), dtype=object)
+    lab[:] = labels
+    preds = lab[idx]
+    preds[~ok] = None
+    return Column.from_values(preds.tolist(), t)
+
+
 class NaiveBayesTextModelMapper(RichModelMapper):
     model = None
+    _table = None       # the device path's model operand (ops.naive_bayes.Table), built on first use
 
     def loadModel(self, rows):
+        self._table = None
         from ..linear.model import LinearModelDataConverter
         lt = LinearModelDataConverter.extractLabelType(self.modelSchema)
         self.model = NaiveBayesTextModelDataConverter(lt).load(rows)
@@ -171,7 +202,42 @@ class NaiveBayesTextModelMapper(RichModelMapper):
         mt = MTable.from_rows([tuple(row)], self.dataSchema)
         return [c.to_list()[0] for c in self._map_columns(mt)]
 
+    def _map_columns_device(self, mt):
+        """The output columns through ``ops.naive_bayes.predict`` (scores, first strict maximum and softmax in one
+        pass over the rows on the device), or None where the gate keeps this table on the host path."""
+        vec_col = self.params.get("vectorCol") if self.params.contains("vectorCol") else self.model["vectorCol"]
+        dev = _dev(mt)
+        v = mt.col(vec_col).values
+        if not isinstance(v, torch.Tensor) and getattr(getattr(v, "val", None), "is_cuda", False):
+            dev = v.val.device                      # a sparse block on the device
+        if not mt.num_rows or not _lib.sized_gate("ALINK_NB_HIP", dev, mt.num_rows, nbops.NB_MIN_ROWS):
+            return None
+        fm = extract_features(mt, None, vec_col, dev)
+        if not nbops.supported(fm):
+            return None
+        bernoulli = self.model["modelType"] == "Bernoulli"
+        if bernoulli and nbops.has_duplicate_index(fm):
+            return None         # the host path sums a twice-stored index before its 0 / 1 check
+        if self._table is None:
+            pi, th = self.model["pi"], self.model["theta"]
+            self._table = nbops.Table(self.minmat, pi + self.phi) if bernoulli else nbops.Table(th, pi)
+        pred, prob, bad = nbops.predict(nbops.predict_rows(fm, self._table.d), self._table, None, bernoulli,
+                                        bool(self.detail_col))
+        if bernoulli and int(bad):
+            raise ValueError("Bernoulli naive Bayes requires 0 or 1 feature values.")
+        labels = self.model["labels"]
+        idx = pred.cpu().numpy().astype(np.int64)
+        t = self.helper.out_types[0]
+        cols = [_label_or_null(labels, np.maximum(idx, 0), idx >= 0, t)]
+        if self.detail_col:
+            cols.append(Column.from_values(_detail_json([java_str(v) for v in labels], prob.cpu().numpy(),
+                                                        quoted=False), Types.STRING))
+        return cols
+
     def _map_columns(self, mt):
+        cols = self._map_columns_device(mt)
+        if cols is not None:
+            return cols
         S = self._scores(mt)
         labels = self.model["labels"]
         if not self.detail_col and len(S):
@@ -179,14 +245,7 @@ class NaiveBayesTextModelMapper(RichModelMapper):
             Sf = np.where(np.isnan(S), -np.inf, S)
             idx = Sf.argmax(1)
             ok = Sf[np.arange(len(Sf)), idx] > -np.inf
-            t = self.helper.out_types[0]
-            if ok.all():
-                return [label_column(labels, idx, t)]
-            lab = np.empty(len(labels), dtype=object)
-            lab[:] = labels
-            preds = lab[idx]
-            preds[~ok] = None
-            return [Column.from_values(preds.tolist(), t)]
+            return [_label_or_null(labels, idx, ok, self.helper.out_types[0])]
         preds, details = [], []
         for s in S:
             best, res = float("-inf"), None

@@ -192,6 +192,10 @@ _SIGNATURES = {
                                    _c_vp, _c_int, _c_vp],
     "alink_evalcluster_rows_csr": [_c_vp, _c_vp, _c_int, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_int,
                                    _c_int, _c_vp, _c_int, _c_vp],
+    "alink_nb_rows_csr": [_c_vp, _c_vp, _c_int, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_vp,
+                          _c_vp, _c_vp, _c_int, _c_vp],
+    "alink_nb_rows_f64": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp,
+                          _c_int, _c_vp],
     "alink_sos_search_f64": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_int, _c_i64, _c_i64, _c_d, _c_vp, _c_vp,
                              _c_vp, _c_int, _c_vp],
     "alink_sos_products_f64": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_i64, _c_i64,
