@@ -9,6 +9,11 @@ MI355X-first design: the reference reduces a ``WeightStat`` (sums, packed ``A^T 
 task and solves there (``setParallelism(1)``).  Here every rank builds its statistics as one
 ``[X|1|b]^T diag(w) [X|1|b]`` GEMM on its device shard, the statistics are summed with a single all-reduce,
 and every rank solves the (k+1)x(k+1) system itself — no gather to one node, no broadcast of the model.
+
+From ``ops.glm.GLM_MIN_ROWS`` rows of a GPU partition on (``ALINK_GLM_HIP``, docs/flags.md), contiguous fp64 rows of at
+most ``GLM_KMAX`` columns and every link but probit take the kernels of ``csrc/glm.hip``: each ``_weight_stats`` of
+``_irls`` becomes one fused ``ops.glm.irls_stats`` pass that reads X once, and the residuals, the summary's sums and
+the mapper's prediction come from ``ops.glm.rows``.  Everything else is the torch path below, unchanged.
 """
 from __future__ import annotations
 
@@ -19,6 +24,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
+from ...ops import _lib, glm as glmops
 from ...ops.gemm import tn_matmul
 from ...common.javafmt import gson_dumps
 from ...common.mapper import ModelMapper, OutputColsHelper
@@ -351,6 +357,22 @@ def _weight_stats(X: torch.Tensor, b: torch.Tensor, w: torch.Tensor) -> np.ndarr
     return buf.cpu().numpy()
 
 
+def _kernel_args(fl: "FamilyLink"):
+    """(family, link, variancePower, linkPower) as ``ops.glm`` takes them."""
+    return (fl.familyName, fl.linkName, getattr(fl.family, "vp", 0.0), getattr(fl.link, "p", 1.0))
+
+
+def _fused_stats(d: "GlmData", fl: "FamilyLink", mode: int, model: Optional["WlsModel"] = None) -> np.ndarray:
+    """``_weight_stats`` of the working label and weight of ``mode`` through one ``ops.glm.irls_stats`` call: the same
+    ``[count, wwSum, G]`` buffer into the same all-reduce, X read once and no ``[n, k+2]`` temporary."""
+    beta, b0 = (model.coefficients, model.intercept) if model is not None else (None, 0.0)
+    wwsum, G = glmops.irls_stats(d.X, d.y, d.w, d.off, beta, b0, *_kernel_args(fl), mode)
+    head = torch.stack([torch.tensor(float(d.X.shape[0]), dtype=d.X.dtype, device=d.X.device), wwsum])
+    buf = torch.cat([head, G.reshape(-1)])
+    comm.all_reduce(buf, "sum")
+    return buf.cpu().numpy()
+
+
 def _wls(stats: np.ndarray, k: int, fit_intercept: bool, reg: float, std_features: bool,
          std_label: bool) -> WlsModel:
     count = stats[0]
@@ -430,18 +452,28 @@ def preprocess(mt: MTable, feature_cols: Sequence[str], label_col: str, weight_c
 
 def _irls(d: GlmData, fl: FamilyLink, reg: float, fit_intercept: bool, num_iter: int, eps: float) -> WlsModel:
     k = d.X.shape[1]
+    fused = glmops.selected(d.X, fl.familyName, fl.linkName)
     if fl.familyName == "gaussian" and fl.linkName == "identity":
-        return _wls(_weight_stats(d.X, d.y - d.off, d.w), k, fit_intercept, reg, True, True)
-    eta0 = fl.predict(fl.family.initialize(d.y, d.w)) - d.off
-    model = _wls(_weight_stats(d.X, eta0, d.w), k, fit_intercept, reg, True, True)
+        stats = _fused_stats(d, fl, glmops.PLAIN) if fused else _weight_stats(d.X, d.y - d.off, d.w)
+        return _wls(stats, k, fit_intercept, reg, True, True)
+    if fused:
+        fl.family.initialize(d.y, d.w)          # the validity checks of the labels, once per training
+        stats = _fused_stats(d, fl, glmops.INIT)
+    else:
+        stats = _weight_stats(d.X, fl.predict(fl.family.initialize(d.y, d.w)) - d.off, d.w)
+    model = _wls(stats, k, fit_intercept, reg, True, True)
     for _ in range(int(num_iter)):
-        beta = torch.as_tensor(model.coefficients, dtype=torch.float64, device=d.X.device)
-        eta = d.X @ beta + model.intercept + d.off
-        mu = fl.fitted(eta)
-        deriv = fl.link.derivative(mu)
-        z = eta - d.off + (d.y - mu) * deriv
-        ww = d.w / (deriv * deriv * fl.family.variance(mu))
-        new = _wls(_weight_stats(d.X, z, ww), k, fit_intercept, reg, False, False)
+        if fused:
+            stats = _fused_stats(d, fl, glmops.STEP, model)
+        else:
+            beta = torch.as_tensor(model.coefficients, dtype=torch.float64, device=d.X.device)
+            eta = d.X @ beta + model.intercept + d.off
+            mu = fl.fitted(eta)
+            deriv = fl.link.derivative(mu)
+            z = eta - d.off + (d.y - mu) * deriv
+            ww = d.w / (deriv * deriv * fl.family.variance(mu))
+            stats = _weight_stats(d.X, z, ww)
+        new = _wls(stats, k, fit_intercept, reg, False, False)
         tol = max([abs(new.intercept - model.intercept)]
                   + [abs(a - b) for a, b in zip(new.coefficients, model.coefficients)])
         model = new
@@ -457,6 +489,10 @@ def train_glm(d: GlmData, p: Params) -> WlsModel:
 
 def glm_residuals(d: GlmData, model: WlsModel, fl: FamilyLink) -> List[torch.Tensor]:
     """[pred, deviance, pearson, working, response] residual columns (``GlmUtil.residualRow``)."""
+    if glmops.selected(d.X, fl.familyName, fl.linkName):
+        r = glmops.rows(d.X, d.y, d.w, d.off, model.coefficients, model.intercept, *_kernel_args(fl),
+                        ("pred", "resid"))
+        return [r["pred"], r["dres"], r["pres"], r["wres"], r["rres"]]
     beta = torch.as_tensor(model.coefficients, dtype=torch.float64, device=d.X.device)
     eta = d.X @ beta + model.intercept + d.off
     pred = fl.fitted(eta)
@@ -479,7 +515,13 @@ def glm_summary(d: GlmData, model: WlsModel, fl: FamilyLink, reg: float, num_ite
     t- and p-values (``diagInvAtWA`` is the true diagonal of ``(A^T W A)^-1``)."""
     from scipy import stats as st
     k = d.X.shape[1]
-    pred, _, pr, _, _ = glm_residuals(d, model, fl)
+    fused = glmops.selected(d.X, fl.familyName, fl.linkName)
+    if fused:       # pred and the sums of the deviance, pearson^2 and w from one row pass
+        r = glmops.rows(d.X, d.y, d.w, d.off, model.coefficients, model.intercept, *_kernel_args(fl),
+                        ("pred", "sums"))
+        pred, sums = r["pred"], r["sums"].tolist()
+    else:
+        pred, _, pr, _, _ = glm_residuals(d, model, fl)
     if fit_intercept:
         if fl.familyName == "gaussian" and fl.linkName == "identity":
             s = _allsum([float((d.w * (d.y - d.off)).sum()), float(d.w.sum())])
@@ -488,11 +530,16 @@ def glm_summary(d: GlmData, model: WlsModel, fl: FamilyLink, reg: float, num_ite
             intercept = _irls(GlmData(d.X[:, :0], d.y, d.w, d.off), fl, reg, True, num_iter, eps).intercept
     else:
         intercept = 0.0
-    null_dev = fl.family.deviance(d.y, fl.link.unlink(intercept + d.off), d.w)
-    dev = fl.family.deviance(d.y, pred, d.w)
-    disp = torch.ones_like(pred) if fl.familyName in ("binomial", "poisson") else pr * pr
-    null_dev_s, dev_s, disp_s, w_s, cnt = _allsum([float(null_dev.sum()), float(dev.sum()), float(disp.sum()),
-                                                  float(d.w.sum()), float(d.y.shape[0])])
+    if fused:       # the null deviance needs the null intercept first: a second pass, sums only
+        null = glmops.rows(d.X, d.y, d.w, d.off, model.coefficients, model.intercept, *_kernel_args(fl), ("sums",),
+                           cnull=intercept)["sums"].tolist()
+        local = [null[1], sums[0], sums[2], sums[3]]
+    else:
+        null_dev = fl.family.deviance(d.y, fl.link.unlink(intercept + d.off), d.w)
+        dev = fl.family.deviance(d.y, pred, d.w)
+        disp = torch.ones_like(pred) if fl.familyName in ("binomial", "poisson") else pr * pr
+        local = [float(null_dev.sum()), float(dev.sum()), float(disp.sum()), float(d.w.sum())]
+    null_dev_s, dev_s, disp_s, w_s, cnt = _allsum(local + [float(d.y.shape[0])])
     count = int(round(cnt))
     fam = fl.familyName
     if fam == "tweedie":
@@ -643,7 +690,28 @@ class GlmModelMapper(ModelMapper):
         m = self.model
         self.fl = FamilyLink(m.familyName, m.variancePower, m.linkName, m.linkPower)
 
+    def _map_columns_device(self, mt: MTable):
+        """The output columns through ``ops.glm.rows`` (linear predictor, unlink and project in one pass over rows
+        built on the environment's GPU), or None where the gate keeps this table on the host path."""
+        m = self.model
+        dev = getattr(getattr(self, "env", None), "device", None)
+        fam, link = self.fl.familyName, self.fl.linkName
+        if dev is None or not mt.num_rows or fam not in glmops.FAMILIES or link not in glmops.LINKS \
+                or not 1 <= len(m.featureColNames or ()) <= glmops.GLM_KMAX \
+                or not _lib.sized_gate("ALINK_GLM_HIP", dev, mt.num_rows, glmops.GLM_MIN_ROWS):
+            return None         # decided before any column is copied to the device
+        X = torch.stack([_col(mt, c, 0.0, dev) for c in m.featureColNames], 1)
+        if not glmops.supported(X, fam, link):
+            return None
+        off = _col(mt, m.offsetColName, 0.0, dev) if m.offsetColName else None
+        r = glmops.rows(X, None, None, off, m.coefficients, m.intercept, *_kernel_args(self.fl),
+                        ("pred", "eta") if self.link_col else ("pred",))
+        return [Column(r["pred"].cpu())] + ([Column(r["eta"].cpu())] if self.link_col else [])
+
     def _map_columns(self, mt: MTable):
+        cols = self._map_columns_device(mt)
+        if cols is not None:
+            return cols
         m = self.model
         cpu = torch.device("cpu")
         X = torch.stack([_col(mt, c, 0.0, cpu) for c in m.featureColNames], 1)
