@@ -17,6 +17,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
+from ...ops import moments as momops
 from ...ops.gemm import tn_matmul
 from ...common.javafmt import gson_dumps
 from ...common.linalg import DenseVector, VectorUtil
@@ -55,6 +56,23 @@ class _PcaModelData:
             setattr(self, f, kw.get(f))
 
 
+def _raw_moments(X: torch.Tensor, d: int):
+    """The former statistics: raw column sums, sums of squares and the Gram matrix, all-reduced in one buffer."""
+    n = torch.tensor([float(X.shape[0])], dtype=torch.float64, device=X.device)
+    buf = torch.cat([n, X.sum(0), (X * X).sum(0), tn_matmul(X, X).reshape(-1)])
+    comm.all_reduce(buf, "sum")
+    cnt = float(buf[0])
+    s = buf[1:1 + d].cpu().numpy()
+    s2 = buf[1 + d:1 + 2 * d].cpu().numpy()
+    G = buf[1 + 2 * d:].reshape(d, d).cpu().numpy()
+    nonconst = [i for i in range(d) if abs(s2[i] - s[i] * s[i] / cnt) > 1e-10]
+    idx = np.asarray(nonconst, dtype=np.int64)
+    s, s2, G = s[idx], s2[idx], G[np.ix_(idx, idx)]
+    cov = (G - np.outer(s, s) / cnt) / (cnt - 1)
+    std = np.sqrt(np.maximum(0.0, (s2 - s * s / cnt) / (cnt - 1)))
+    return idx, s / cnt, cnt, cov, std
+
+
 def train_pca(mt: MTable, params: Params, env) -> List[tuple]:
     dev = env.device
     k = int(params.get("k"))
@@ -68,18 +86,17 @@ def train_pca(mt: MTable, params: Params, env) -> List[tuple]:
     X = fm.to_dense().to(torch.float64)
     if X.shape[1] < d:
         X = torch.nn.functional.pad(X, (0, d - X.shape[1]))
-    n = torch.tensor([float(X.shape[0])], dtype=torch.float64, device=X.device)
-    buf = torch.cat([n, X.sum(0), (X * X).sum(0), tn_matmul(X, X).reshape(-1)])
-    comm.all_reduce(buf, "sum")
-    cnt = float(buf[0])
-    s = buf[1:1 + d].cpu().numpy()
-    s2 = buf[1 + d:1 + 2 * d].cpu().numpy()
-    G = buf[1 + 2 * d:].reshape(d, d).cpu().numpy()
-    nonconst = [i for i in range(d) if abs(s2[i] - s[i] * s[i] / cnt) > 1e-10]
-    idx = np.asarray(nonconst, dtype=np.int64)
-    s, s2, G = s[idx], s2[idx], G[np.ix_(idx, idx)]
-    cov = (G - np.outer(s, s) / cnt) / (cnt - 1)
-    std = np.sqrt(np.maximum(0.0, (s2 - s * s / cnt) / (cnt - 1)))
+    shift = momops.shared_shift(X)
+    if shift is not None:
+        # one shifted moment pass: the centred sums S = C - t t^T / n do not cancel for columns of a large mean
+        cnt, mean, S = momops.covariance(X, shift)
+        mean, S = mean.cpu().numpy(), S.cpu().numpy()
+        idx = np.asarray([i for i in range(d) if abs(S[i, i]) > 1e-10], dtype=np.int64)
+        means = mean[idx]
+        cov = S[np.ix_(idx, idx)] / (cnt - 1)
+        std = np.sqrt(np.maximum(0.0, np.diagonal(cov)))
+    else:
+        idx, means, cnt, cov, std = _raw_moments(X, d)
     if ctype == "CORR":
         M = cov / np.outer(std, std)
         np.fill_diagonal(M, 1.0)
@@ -98,7 +115,7 @@ def train_pca(mt: MTable, params: Params, env) -> List[tuple]:
         if vec[np.argmax(np.abs(vec[:, j])), j] < 0:
             vec[:, j] = -vec[:, j]
     model = _PcaModelData(featureColNames=list(cols) if cols and not vcol else None, vectorColName=vcol,
-                          pcaType=ctype, means=(s / cnt).tolist(), stddevs=std.tolist(), p=k,
+                          pcaType=ctype, means=means.tolist(), stddevs=std.tolist(), p=k,
                           **{"lambda": lam.tolist()}, coef=vec.T.tolist(), cov=cov.tolist(),
                           idxNonEqual=[int(i) for i in idx], nx=d)
     meta = Params().set("featureCols", list(cols) if cols and not vcol else None).set("vectorCol", vcol) \
@@ -135,6 +152,15 @@ class PcaModelMapper(ModelMapper):
             score_std = np.sqrt(np.einsum("ij,ik,jk->i", self.coef, self.coef, cov))
         self.mean, self.std, self.score_std = mean, std, score_std
         self.nx = nx
+        # the same projection per original column, for the fused kernel (ops/moments.pca_project): a column that
+        # ``_project`` drops or zeroes gets scale 0, one it passes through unscaled mean 0 and scale 1
+        ok = np.abs(std) > 1e-12
+        self.col_mean, self.col_scale = np.zeros(nx), np.zeros(nx)
+        self.col_mean[self.idx] = np.where(ok, mean, 0.0)
+        self.col_scale[self.idx] = np.where(ok, std, 1.0 if nne == nx else 0.0)
+        self.table = np.zeros((self.coef.shape[0], nx))
+        self.table[:, self.idx] = self.coef
+        self._images = {}           # the table's lane-ordered image per device
 
     def _map_columns(self, mt):
         from ..linear.model import _dev
@@ -143,7 +169,16 @@ class PcaModelMapper(ModelMapper):
         if fm.is_sparse:
             fm.set_ncols(self.nx)
         if dev.type == "cuda" and mt.num_rows:
-            P = self._project_device(fm.to_dense().double())
+            X = fm.to_dense().double()
+            if X.shape[1] < self.nx:
+                X = torch.nn.functional.pad(X, (0, self.nx - X.shape[1]))
+            if X.shape[1] == self.nx and self.coef.shape[0] >= 1 and momops.selected(X):
+                if dev not in self._images:
+                    self._images[dev] = momops.project_table(self.table, dev)
+                P = momops.pca_project(X, self.col_mean, self.col_scale, self._images[dev], self.score_std) \
+                    .cpu().numpy()
+            else:
+                P = self._project_device(X)
         else:
             P = self._project(fm.to_dense().double().numpy())
         from ... import _native

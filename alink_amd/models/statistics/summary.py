@@ -18,6 +18,7 @@ from typing import Any, List, Optional, Sequence
 import numpy as np
 import torch
 
+from ...ops import moments as momops
 from ...ops.gemm import tn_matmul
 from ...common.javafmt import gson_dumps
 from ...common.linalg import DenseMatrix, DenseVector, SparseVector, VectorUtil
@@ -339,6 +340,10 @@ def _pearson_pairwise(X: torch.Tensor, valid: torch.Tensor) -> np.ndarray:
 
 
 def _pearson(X: torch.Tensor) -> np.ndarray:
+    shift = momops.shared_shift(X)
+    if shift is not None:       # one shifted moment pass: no cancellation for columns of a large mean
+        n, _, S = momops.covariance(X, shift)
+        return _corr_of_cov(S / max(n - 1, 1.0))
     n_loc = torch.tensor([float(X.shape[0])], dtype=torch.float64, device=X.device)
     s = X.sum(0)
     G = tn_matmul(X, X)
@@ -347,7 +352,10 @@ def _pearson(X: torch.Tensor) -> np.ndarray:
     d = X.shape[1]
     n = float(buf[0])
     s, G = buf[1:1 + d], buf[1 + d:].reshape(d, d)
-    cov = (G - torch.outer(s, s) / n) / max(n - 1, 1.0)
+    return _corr_of_cov((G - torch.outer(s, s) / n) / max(n - 1, 1.0))
+
+
+def _corr_of_cov(cov: torch.Tensor) -> np.ndarray:
     sd = torch.sqrt(torch.clamp(torch.diagonal(cov), min=0.0))
     corr = cov / torch.outer(sd, sd)
     corr = torch.where(torch.outer(sd, sd) == 0, torch.full_like(corr, float("nan")), corr)

@@ -47,6 +47,25 @@ __device__ __forceinline__ d4_t mf64(double a, double b, d4_t c) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
 
+// upper tile t of an NT x NT tile matrix, tile rows ascending, then tile columns (the Gram kernels of glm.hip and
+// moments.hip deal these tiles to the waves)
+constexpr int tile_a(int nt, int t) {
+    int ta = 0;
+    while (t >= nt - ta) {
+        t -= nt - ta;
+        ++ta;
+    }
+    return ta;
+}
+constexpr int tile_b(int nt, int t) {
+    int ta = 0;
+    while (t >= nt - ta) {
+        t -= nt - ta;
+        ++ta;
+    }
+    return ta + t;
+}
+
 // the four lanes (lane & 15 fixed) that share a data row: both partners add the same two values at each step, so
 // every one of them ends with the same bits
 __device__ __forceinline__ double group_sum(double v) {

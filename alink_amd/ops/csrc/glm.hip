@@ -39,6 +39,8 @@ namespace {
 using d64::d2_t;
 using d64::d4_t;
 using d64::mf64;
+using d64::tile_a;
+using d64::tile_b;
 
 constexpr double EPSILON = 1e-16, DELTA = 0.1, JAVA_MAX_VALUE = 1.7976931348623157e308, JAVA_MIN_VALUE = 4.9e-324;
 constexpr int GLM_KMAX = 126;
@@ -212,24 +214,6 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
-}
-
-// upper tile t of an NT x NT tile matrix, tile rows ascending, then tile columns
-constexpr int tile_a(int nt, int t) {
-    int ta = 0;
-    while (t >= nt - ta) {
-        t -= nt - ta;
-        ++ta;
-    }
-    return ta;
-}
-constexpr int tile_b(int nt, int t) {
-    int ta = 0;
-    while (t >= nt - ta) {
-        t -= nt - ta;
-        ++ta;
-    }
-    return ta + t;
 }
 
 template <int NT>

@@ -1,0 +1,488 @@
+// Second-moment statistics and the PCA projection on gfx950 / MI355X (ops/moments.py), for contiguous fp64 rows
+// X [n, d] with 1 <= d <= 1024.
+//
+// alink_moments_f64: one pass that gives out = [t | C], t = sum_i y_i, C = sum_i y_i y_i^T over the shifted rows
+// y_i = x_i - shift (shift [d] or null: zero).  The columns are cut into blocks of MB = 128 (8 MFMA tiles of 16); a
+// unit of work is (row chunk, block pair A <= B).  A workgroup of 4 waves walks its chunk 64 rows at a time:
+//   load    four lanes per row (tid >> 2 the row, tid & 3 = sub) read the row's slice of block A (and of block B in
+//           an off-diagonal unit), lane sub the 4-column groups 4 j + sub (d64::load_group: two 16-byte loads where d
+//           is even and X 16-byte aligned, four 8-byte loads otherwise; no address outside the row is loaded),
+//           subtract the shift (staged once per unit in LDS) and store the shifted slice to the row's LDS slot; the
+//           columns behind d and the rows behind the chunk are zero.
+//   tiles   after one barrier, v_mfma_f64_16x16x4_f64 over four consecutive rows per instruction, with the operand
+//           and result maps of dense64_mfma.h: A[m][g] = y_{i0+g}[16 ta + m], B[g][m] = y_{i0+g}[16 tb + m], so
+//           slot q of a lane is C[16 ta + g + 4 q][16 tb + m].  Accumulators stay in registers for the whole chunk.
+//           diagonal unit (block of NT tiles): the NT (NT + 1) / 2 upper tiles (tile_a / tile_b order) and behind
+//             them NT "ones" tiles, A = 1.0 on every lane, whose every result row is the column sum t of tile tb:
+//             at most 36 + 8 tiles; tile t belongs to wave t mod 4.  With NT <= 2 (2 or 5 tiles) the waves split
+//             the batch's rows instead, and their partials are added in wave order at the chunk's end.
+//           off-diagonal unit (A < B, so A has 8 tiles, B has nb <= 8): wave w owns the tile rows 2 w and 2 w + 1
+//             and all nb tile columns, 16 tiles at most.
+//           Both rules depend on (d, A, B) alone, and t comes out of the matrix instruction: nothing depends on
+//           the grid.
+//   merge   part [nchunk, d + d d] holds each chunk's t and the entries of its upper tiles; one lane per output
+//           element adds them in chunk order and mirrors the triangle, so C is exactly symmetric.  No float atomics:
+//           the same bits for every grid and run.
+// The diagonal units of the full blocks, the diagonal unit of a last block of fewer tiles and the off-diagonal units
+// are three launches (each kernel has its own tile count at compile time); they write disjoint parts of `part`.
+// The LDS row stride is 16 NT + 16 doubles, so the four lane groups of a tile read start 32 banks apart.
+//
+// alink_pca_project_f64: P[i, j] = sum_c z_ic T[j, c] / sstd[j], z_ic = (x_ic - mean[c]) / scale[c] (a true fp64
+// division; scale[c] = 0 gives exactly 0 whatever the cell holds), on the shared tile loop of dense64_mfma.h: 64
+// rows per workgroup, the table T as the lane-ordered image staged in LDS per (block, dim chunk), the row chunk
+// transformed in registers right after the guarded load (load_shifted = load_group + shift_group, as the moment pass).  The epilogue
+// divides by sstd[j] and writes P [n, k] only.
+//
+// All arithmetic is fp64, no contraction: the only fused operation is the matrix instruction.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "dense64_mfma.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+using namespace d64;
+
+constexpr int MB = 128;             // columns per block: 8 tiles, the widest triangle one workgroup holds
+constexpr int MOMENTS_DMAX = 1024;
+
+// The shift of one loaded group: v[s] - sh[so + s] for the four dims j0 .. j0 + 3 of a row (v by load_group);
+// SCALED: then divided by sc[so + s], a zero scale giving exactly 0 (also for a non-finite cell).  Zero outside
+// [0, d) or when the row is not `ok`.  SCALED reads sh / sc for dims inside the row only (global tables of d
+// entries); otherwise sh[so .. so + 3] is read whole (an LDS slice, zero behind d), which keeps the guards flat
+// selects and lets a caller keep many loads in flight.
+template <bool SCALED>
+__device__ __forceinline__ d4_t shift_group(d4_t v, bool ok, int j0, int d, const double* __restrict__ sh,
+                                            const double* __restrict__ sc, int so) {
+    d4_t r;
+    if (SCALED) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            double y = 0.0;
+            if (ok && j0 + s < d) {
+                const double c = sc[so + s];
+                y = c == 0.0 ? 0.0 : (v[s] - sh[so + s]) / c;
+            }
+            r[s] = y;
+        }
+    } else {
+        const d4_t h = *reinterpret_cast<const d4_t*>(sh + so);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) r[s] = (ok && j0 + s < d) ? v[s] - h[s] : 0.0;
+    }
+    return r;
+}
+
+// the guarded load and its shift in one: the shifted load of the moment pass and of the projection
+template <bool VEC, bool SCALED>
+__device__ __forceinline__ d4_t load_shifted(const double* __restrict__ xr, bool ok, int j0, int d,
+                                             const double* __restrict__ sh, const double* __restrict__ sc, int so) {
+    return shift_group<SCALED>(load_group<VEC>(xr, ok, j0, d), ok, j0, d, sh, sc, so);
+}
+
+// One row's slice of NT tiles starting at column c0 into its LDS slot: lane sub of the row's four lanes the
+// 4-column groups 4 j + sub.  All NT loads are issued before the first is used (load_slice), then shifted and
+// stored (store_slice = the rest of load_shifted).
+template <int NT, bool VEC>
+__device__ __forceinline__ void load_slice(d4_t (&v)[NT], const double* __restrict__ xr, bool ok, int c0, int d,
+                                           int sub) {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) v[j] = load_group<VEC>(xr, ok, c0 + 4 * (4 * j + sub), d);
+}
+
+template <int NT>
+__device__ __forceinline__ void store_slice(double* __restrict__ slot, const d4_t (&v)[NT], bool ok, int c0, int d,
+                                            const double* __restrict__ sh, int sub) {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int q = 4 * (4 * j + sub);
+        *reinterpret_cast<d4_t*>(slot + q) = shift_group<false>(v[j], ok, c0 + q, d, sh, nullptr, q);
+    }
+}
+
+// the shift of the NT tiles from column c0 on into sh (zero behind d or without a shift); threads t0 .. t0 + 16 NT
+__device__ __forceinline__ void stage_shift(double* __restrict__ sh, const double* __restrict__ shift, int c0, int d,
+                                            int nt, int t) {
+    if (t >= 0 && t < 16 * nt) sh[t] = (shift != nullptr && c0 + t < d) ? shift[c0 + t] : 0.0;
+}
+
+template <int NT>
+struct Diag {
+    static constexpr int S = 16 * NT + 16;              // LDS row stride in doubles
+    static constexpr int TU = NT * (NT + 1) / 2;        // upper tiles
+    static constexpr int T = TU + NT;                   // and the ones tiles behind them
+    static constexpr bool SPLIT = NT <= 2;              // the waves split the rows, not the tiles
+    static constexpr int MAXT = SPLIT ? T : (T + 3) / 4;    // accumulator tiles per wave
+
+    // slot s of wave WAVE
+    static constexpr int tile(int wave, int s) { return SPLIT ? s : wave + 4 * s; }
+
+    // one step of four rows for the wave's slots s, the tile indices compile-time
+    template <int WAVE, int s = 0>
+    static __device__ __forceinline__ void step(d4_t (&acc)[MAXT], const double (&v)[NT]) {
+        if constexpr (s < MAXT) {
+            constexpr int t = tile(WAVE, s);
+            // the tile's indices as constants of their own: left inside the call, their loops run on the device
+            constexpr int ta = t < TU ? tile_a(NT, t) : 0, tb = t < TU ? tile_b(NT, t) : t - TU;
+            if constexpr (t < TU) acc[s] = mf64(v[ta], v[tb], acc[s]);
+            else if constexpr (t < T) acc[s] = mf64(1.0, v[tb], acc[s]);
+            step<WAVE, s + 1>(acc, v);
+        }
+    }
+
+    // the products of the staged batch: all 64 rows for the wave's tiles, or the wave's 16 rows for every tile
+    template <int WAVE>
+    static __device__ __forceinline__ void batch(d4_t (&acc)[MAXT], const double* __restrict__ rows, int wave, int g,
+                                                 int m) {
+        const int base = SPLIT ? 16 * wave : 0;
+#pragma unroll 2
+        for (int r4 = 0; r4 < (SPLIT ? 4 : 16); ++r4) {
+            const int row = base + 4 * r4 + g;
+            double v[NT];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) v[t] = rows[row * S + 16 * t + m];
+            step<WAVE>(acc, v);
+        }
+    }
+
+    // pc = the chunk's [t | C]: the upper tiles' entries and, from result row 0 of a ones tile, t
+    template <int WAVE, int s = 0>
+    static __device__ __forceinline__ void store(const d4_t (&acc)[MAXT], double* __restrict__ pc, int d, int c0,
+                                                 int g, int m) {
+        if constexpr (s < MAXT) {
+            constexpr int t = tile(WAVE, s);
+            if constexpr (t < TU) {
+                constexpr int ta = tile_a(NT, t), tb = tile_b(NT, t);
+                const int cb = c0 + 16 * tb + m;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int ra = c0 + 16 * ta + g + 4 * q;
+                    if (ra < d && cb < d) pc[d + (int64_t)ra * d + cb] = acc[s][q];
+                }
+            } else if constexpr (t < T) {
+                const int cb = c0 + 16 * (t - TU) + m;
+                if (g == 0 && cb < d) pc[cb] = acc[s][0];
+            }
+            store<WAVE, s + 1>(acc, pc, d, c0, g, m);
+        }
+    }
+};
+
+// the diagonal units (chunk, block blk0 + b), b < nblk, every block of NT tiles
+template <int NT, bool VEC>
+__global__ __launch_bounds__(256) void moments_diag_kernel(const double* __restrict__ X, int64_t n, int d,
+                                                           const double* __restrict__ shift, int blk0, int nblk,
+                                                           int64_t chunk_rows, int64_t nchunk,
+                                                           double* __restrict__ part) {
+    using D = Diag<NT>;
+    constexpr int S = D::S;
+    __shared__ __attribute__((aligned(32))) double rows[64 * S];
+    __shared__ __attribute__((aligned(32))) double sh[16 * NT];
+    __shared__ __attribute__((aligned(32))) double red[D::SPLIT ? 4 * D::T * 256 : 1];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = tid >> 2, sub = tid & 3;
+    const int m = lane & 15, g = lane >> 4;
+    const int64_t P = d + (int64_t)d * d;
+    for (int64_t u = blockIdx.x; u < nchunk * nblk; u += gridDim.x) {
+        const int64_t c = u / nblk;
+        const int c0 = (blk0 + (int)(u - c * nblk)) * MB;
+        const int64_t r0 = c * chunk_rows;
+        const int64_t r1 = r0 + chunk_rows < n ? r0 + chunk_rows : n;
+        stage_shift(sh, shift, c0, d, NT, tid);     // the previous unit's reads ended at its last barrier
+        __syncthreads();
+        d4_t acc[D::MAXT];
+#pragma unroll
+        for (int s = 0; s < D::MAXT; ++s) acc[s] = d4_t{0.0, 0.0, 0.0, 0.0};
+        for (int64_t bb = r0; bb < r1; bb += 64) {
+            const int64_t i = bb + r;
+            const bool ok = i < r1;
+            d4_t v[NT];
+            load_slice<NT, VEC>(v, X + (ok ? i : r0) * (int64_t)d, ok, c0, d, sub);
+            store_slice<NT>(rows + r * S, v, ok, c0, d, sh, sub);
+            __syncthreads();
+            switch (wave) {
+                case 0: D::template batch<0>(acc, rows, wave, g, m); break;
+                case 1: D::template batch<1>(acc, rows, wave, g, m); break;
+                case 2: D::template batch<2>(acc, rows, wave, g, m); break;
+                default: D::template batch<3>(acc, rows, wave, g, m); break;
+            }
+            __syncthreads();        // the batch's reads are done before the next one is staged
+        }
+        double* __restrict__ pc = part + c * P;
+        if (D::SPLIT) {
+#pragma unroll
+            for (int s = 0; s < D::MAXT; ++s)
+                *reinterpret_cast<d4_t*>(red + ((wave * D::T + s) * 64 + lane) * 4) = acc[s];
+            __syncthreads();
+            if (wave == 0) {
+#pragma unroll
+                for (int s = 0; s < D::MAXT; ++s) {
+                    d4_t a = *reinterpret_cast<const d4_t*>(red + (s * 64 + lane) * 4);
+                    for (int ws = 1; ws < 4; ++ws)
+                        a += *reinterpret_cast<const d4_t*>(red + ((ws * D::T + s) * 64 + lane) * 4);
+                    acc[s] = a;
+                }
+                D::template store<0>(acc, pc, d, c0, g, m);
+            }
+            __syncthreads();
+        } else {
+            switch (wave) {
+                case 0: D::template store<0>(acc, pc, d, c0, g, m); break;
+                case 1: D::template store<1>(acc, pc, d, c0, g, m); break;
+                case 2: D::template store<2>(acc, pc, d, c0, g, m); break;
+                default: D::template store<3>(acc, pc, d, c0, g, m); break;
+            }
+        }
+    }
+}
+
+constexpr int OS = MB + 16;         // LDS row stride of the off-diagonal slices
+
+// The products of the staged batch of an off-diagonal unit: wave WAVE's tile rows 2 WAVE and 2 WAVE + 1 against the
+// nb tile columns of B (FULL: nb = 8, no test), acc[8 i + j] the tile (2 WAVE + i, j).
+template <int WAVE, bool FULL>
+__device__ __forceinline__ void off_batch(d4_t (&acc)[16], const double* __restrict__ ra, const double* __restrict__ rb,
+                                          int nb, int g, int m) {
+#pragma unroll 2
+    for (int r4 = 0; r4 < 16; ++r4) {
+        const int row = 4 * r4 + g;
+        const double a0 = ra[row * OS + 32 * WAVE + m], a1 = ra[row * OS + 32 * WAVE + 16 + m];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (FULL || j < nb) {
+                const double b = rb[row * OS + 16 * j + m];
+                acc[j] = mf64(a0, b, acc[j]);
+                acc[8 + j] = mf64(a1, b, acc[8 + j]);
+            }
+        }
+    }
+}
+
+template <int WAVE>
+__device__ __forceinline__ void off_store(const d4_t (&acc)[16], double* __restrict__ pc, int d, int ca, int cb0,
+                                          int g, int m) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int cb = cb0 + 16 * j + m;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int ra = ca + 16 * (2 * WAVE + i) + g + 4 * q;
+                if (ra < d && cb < d) pc[d + (int64_t)ra * d + cb] = acc[8 * i + j][q];
+            }
+        }
+    }
+}
+
+// the off-diagonal units (chunk, A < B) of nblk >= 2 blocks, the pairs in the order A ascending, then B
+template <bool VEC>
+__global__ __launch_bounds__(256) void moments_off_kernel(const double* __restrict__ X, int64_t n, int d,
+                                                          const double* __restrict__ shift, int nblk,
+                                                          int64_t chunk_rows, int64_t nchunk,
+                                                          double* __restrict__ part) {
+    __shared__ __attribute__((aligned(32))) double ra[64 * OS];
+    __shared__ __attribute__((aligned(32))) double rb[64 * OS];
+    __shared__ __attribute__((aligned(32))) double sh[2 * MB];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = tid >> 2, sub = tid & 3;
+    const int m = lane & 15, g = lane >> 4;
+    const int64_t P = d + (int64_t)d * d;
+    const int npair = nblk * (nblk - 1) / 2;
+    for (int64_t u = blockIdx.x; u < nchunk * npair; u += gridDim.x) {
+        const int64_t c = u / npair;
+        int p = (int)(u - c * npair), A = 0;
+        while (p >= nblk - 1 - A) {
+            p -= nblk - 1 - A;
+            ++A;
+        }
+        const int ca = A * MB, cb0 = (A + 1 + p) * MB;
+        const int nb = d - cb0 >= MB ? 8 : (d - cb0 + 15) / 16;
+        const int64_t r0 = c * chunk_rows;
+        const int64_t r1 = r0 + chunk_rows < n ? r0 + chunk_rows : n;
+        stage_shift(sh, shift, ca, d, 8, tid);
+        stage_shift(sh + MB, shift, cb0, d, 8, tid - MB);
+        __syncthreads();
+        d4_t acc[16];
+#pragma unroll
+        for (int s = 0; s < 16; ++s) acc[s] = d4_t{0.0, 0.0, 0.0, 0.0};
+        for (int64_t bb = r0; bb < r1; bb += 64) {
+            const int64_t i = bb + r;
+            const bool ok = i < r1;
+            const double* __restrict__ xr = X + (ok ? i : r0) * (int64_t)d;
+            d4_t va[8], vb[8];
+            load_slice<8, VEC>(va, xr, ok, ca, d, sub);
+            load_slice<8, VEC>(vb, xr, ok, cb0, d, sub);
+            store_slice<8>(ra + r * OS, va, ok, ca, d, sh, sub);
+            store_slice<8>(rb + r * OS, vb, ok, cb0, d, sh + MB, sub);
+            __syncthreads();
+            if (nb == 8) {
+                switch (wave) {
+                    case 0: off_batch<0, true>(acc, ra, rb, nb, g, m); break;
+                    case 1: off_batch<1, true>(acc, ra, rb, nb, g, m); break;
+                    case 2: off_batch<2, true>(acc, ra, rb, nb, g, m); break;
+                    default: off_batch<3, true>(acc, ra, rb, nb, g, m); break;
+                }
+            } else {
+                switch (wave) {
+                    case 0: off_batch<0, false>(acc, ra, rb, nb, g, m); break;
+                    case 1: off_batch<1, false>(acc, ra, rb, nb, g, m); break;
+                    case 2: off_batch<2, false>(acc, ra, rb, nb, g, m); break;
+                    default: off_batch<3, false>(acc, ra, rb, nb, g, m); break;
+                }
+            }
+            __syncthreads();        // the batch's reads are done before the next one is staged
+        }
+        double* __restrict__ pc = part + c * P;
+        switch (wave) {
+            case 0: off_store<0>(acc, pc, d, ca, cb0, g, m); break;
+            case 1: off_store<1>(acc, pc, d, ca, cb0, g, m); break;
+            case 2: off_store<2>(acc, pc, d, ca, cb0, g, m); break;
+            default: off_store<3>(acc, pc, d, ca, cb0, g, m); break;
+        }
+    }
+}
+
+// out [d + d d] = [t | C]: every element the sum of its chunk partials in chunk order, the lower triangle read from
+// the upper
+__global__ __launch_bounds__(256) void moments_merge_kernel(int d, int64_t nchunk, const double* __restrict__ part,
+                                                            double* __restrict__ out) {
+    const int64_t P = d + (int64_t)d * d;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= P) return;
+    int64_t src = e;
+    if (e >= d) {
+        const int a = (int)((e - d) / d), b = (int)((e - d) - (int64_t)a * d);
+        src = d + (a <= b ? (int64_t)a * d + b : (int64_t)b * d + a);
+    }
+    double s = part[src];
+    int64_t c = 1;
+    for (; c + 8 <= nchunk; c += 8) {       // eight loads in flight, added in chunk order
+        double t[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) t[u] = part[(c + u) * P + src];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += t[u];
+    }
+    for (; c < nchunk; ++c) s += part[c * P + src];
+    out[e] = s;
+}
+
+// img: the image of T [k, nx] (dense64_mfma.h), nblk blocks of 16 NT table rows, ndch = ceil(nx / 32) dim chunks
+template <int NT, bool VEC>
+__global__ __launch_bounds__(64 * WAVES) void pca_project_kernel(
+        const double* __restrict__ X, int64_t n, int nx, const double* __restrict__ mean,
+        const double* __restrict__ scale, const double* __restrict__ img, int k, int nblk, int ndch,
+        const double* __restrict__ sstd, double* __restrict__ P) {
+    __shared__ __attribute__((aligned(16))) double cent[NT * 512];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int m = lane & 15, g = lane >> 4;
+    const int64_t nbatch = (n + ROWS - 1) / ROWS;
+    for (int64_t b = blockIdx.x; b < nbatch; b += gridDim.x) {
+        const int64_t row = b * ROWS + wave * 16 + m;
+        const bool row_ok = row < n;
+        const double* __restrict__ xr = X + (row_ok ? row : 0) * (int64_t)nx;
+        for (int cb = 0; cb < nblk; ++cb) {
+            d4_t acc[NT];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[t] = d4_t{0.0, 0.0, 0.0, 0.0};
+            for (int dc = 0; dc < ndch; ++dc) {
+                // this lane's dims of the row, standardised (zero outside the row), then the table block of the chunk
+                double xb[2][4];
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const int j0 = dc * DCH + 16 * u + 4 * g;
+                    const d4_t v = load_shifted<VEC, true>(xr, row_ok, j0, nx, mean, scale, j0);
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) xb[u][s] = v[s];
+                }
+                stage<NT>(cent, img, cb, ndch, dc);
+#pragma unroll
+                for (int u = 0; u < 2; ++u) mfma_group<NT>(acc, cent, xb[u], u, g, m);
+            }
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int j = (cb * NT + t) * 16 + g + 4 * q;
+                    if (row_ok && j < k) P[row * (int64_t)k + j] = acc[t][q] / sstd[j];
+                }
+            }
+        }
+    }
+}
+
+}  // namespace
+
+#define ALINK_MOMENTS_DIAG(nt, vec, blocks, st, ...)                                                               \
+    do {                                                                                                           \
+        switch (nt) {                                                                                              \
+            case 1: ALINK_D64_LAUNCH_VEC(moments_diag_kernel, 1, vec, blocks, st, __VA_ARGS__); break;             \
+            case 2: ALINK_D64_LAUNCH_VEC(moments_diag_kernel, 2, vec, blocks, st, __VA_ARGS__); break;             \
+            case 3: ALINK_D64_LAUNCH_VEC(moments_diag_kernel, 3, vec, blocks, st, __VA_ARGS__); break;             \
+            case 4: ALINK_D64_LAUNCH_VEC(moments_diag_kernel, 4, vec, blocks, st, __VA_ARGS__); break;             \
+            case 5: ALINK_D64_LAUNCH_VEC(moments_diag_kernel, 5, vec, blocks, st, __VA_ARGS__); break;             \
+            case 6: ALINK_D64_LAUNCH_VEC(moments_diag_kernel, 6, vec, blocks, st, __VA_ARGS__); break;             \
+            case 7: ALINK_D64_LAUNCH_VEC(moments_diag_kernel, 7, vec, blocks, st, __VA_ARGS__); break;             \
+            default: ALINK_D64_LAUNCH_VEC(moments_diag_kernel, 8, vec, blocks, st, __VA_ARGS__); break;            \
+        }                                                                                                          \
+    } while (0)
+
+extern "C" {
+
+// One moment pass over X [n, d] (1 <= d <= 1024), shift [d] or null: out [d + d d] = [t | C] through
+// nchunk = ceil(n / crows) row chunks (crows a multiple of 64) whose partials part [nchunk, d + d d] are merged in
+// chunk order.  grid > 0 caps the workgroups of every launch; it changes no bit of the result.
+int alink_moments_f64(const double* X, int64_t n, int d, const double* shift, int64_t crows, int64_t nchunk,
+                      double* part, double* out, int grid, void* stream) {
+    if (n <= 0) return 0;
+    if (d < 1 || d > MOMENTS_DMAX || n >= (1ll << 31)) return 1;
+    if (crows < 64 || crows % 64 != 0 || nchunk != (n + crows - 1) / crows) return 1;
+    if (X == nullptr || part == nullptr || out == nullptr) return 1;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const bool vec = vec_ok(d, X);
+    const int nfull = d / MB, ntl = (d % MB + 15) / 16, nblk = nfull + (ntl > 0);
+    auto blocks = [&](int64_t units) { return (unsigned)(grid > 0 && grid < units ? grid : units); };
+    if (nfull > 0)
+        ALINK_MOMENTS_DIAG(8, vec, blocks(nchunk * nfull), st, X, n, d, shift, 0, nfull, crows, nchunk, part);
+    if (ntl > 0) ALINK_MOMENTS_DIAG(ntl, vec, blocks(nchunk), st, X, n, d, shift, nfull, 1, crows, nchunk, part);
+    if (nblk > 1) {
+        const unsigned ob = blocks(nchunk * (nblk * (nblk - 1) / 2));
+        if (vec)
+            hipLaunchKernelGGL(moments_off_kernel<true>, dim3(ob), dim3(256), 0, st, X, n, d, shift, nblk, crows,
+                               nchunk, part);
+        else
+            hipLaunchKernelGGL(moments_off_kernel<false>, dim3(ob), dim3(256), 0, st, X, n, d, shift, nblk, crows,
+                               nchunk, part);
+    }
+    const int64_t P = d + (int64_t)d * d;
+    hipLaunchKernelGGL(moments_merge_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, d, nchunk, part,
+                       out);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// P [n, k] = ((X - mean) / scale) T^T / sstd for X [n, nx] (1 <= nx <= 1024), mean / scale [nx], sstd [k]; img: the
+// image of T [k, nx] by ``ops/kmeans_dense64.centroid_image`` (its tiles-per-block and block count follow from k).
+int alink_pca_project_f64(const double* X, int64_t n, int nx, const double* mean, const double* scale,
+                          const double* img, int k, const double* sstd, double* P, int grid, void* stream) {
+    if (n <= 0) return 0;
+    if (nx < 1 || nx > MOMENTS_DMAX || k < 1 || n >= (1ll << 31)) return 1;
+    int nt = 1;         // ``tiles(k)``: the power of two that covers k, at most 8
+    while (nt < 8 && 16 * nt < k) nt *= 2;
+    const int nblk = (k + 16 * nt - 1) / (16 * nt);
+    if (X == nullptr || mean == nullptr || scale == nullptr || img == nullptr || sstd == nullptr || P == nullptr)
+        return 1;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int ndch = (nx + DCH - 1) / DCH;
+    ALINK_D64_LAUNCH(pca_project_kernel, nt, 1, 2, 4, 8, vec_ok(nx, X), row_blocks(n, grid, 4096), st, X, n, nx, mean,
+                     scale, img, k, nblk, ndch, sstd, P);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+}  // extern "C"

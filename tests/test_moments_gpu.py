@@ -1,0 +1,160 @@
+"""The moment pass and the fused PCA projection (ops/csrc/moments.hip) on the GPU against longdouble oracles and
+themselves (grids, alignment), and the correlation and PCA operators on columns of a large mean against a two-pass
+longdouble oracle and against ``ALINK_MOMENTS_HIP=0``."""
+import functools
+import itertools
+import json
+
+import numpy as np
+import pytest
+import torch
+
+from alink_amd.ops import _lib, moments as M
+
+pytestmark = pytest.mark.gpu
+L = np.longdouble
+U = L(2) ** -53
+DS, NS = (1, 2, 15, 16, 17, 127, 128, 129, 257, 1024), (1, 3, 63, 64, 65, 200)
+# d and n taken in turn, and two and three blocks over several chunks as well
+CASES = list(zip(DS, itertools.cycle(NS))) + [(129, 200), (257, 200)]
+
+
+@functools.lru_cache(maxsize=None)
+def moment_case(d, n, shifted):
+    rng = np.random.default_rng(1000 * d + n)
+    X = rng.standard_normal((n, d)) + 3.0
+    shift = X[0] + rng.standard_normal(d) if shifted else None
+    Y = X.astype(L) - (shift.astype(L) if shifted else 0)
+    return X, shift, Y.sum(0), Y.T @ Y, np.abs(Y).sum(0), np.abs(Y).T @ np.abs(Y)
+
+
+def run_moments(X, shift, **kw):
+    calls = M.MOMENTS_CALLS
+    t, C = M.moments(X, None if shift is None else torch.from_numpy(shift), **kw)
+    assert M.MOMENTS_CALLS > calls
+    return t, C
+
+
+@pytest.mark.parametrize("shifted", [False, True])
+@pytest.mark.parametrize("chunk_rows", [0, 64])
+@pytest.mark.parametrize("d,n", CASES)
+def test_moments_against_the_oracle(d, n, chunk_rows, shifted):
+    """t and C against the longdouble sums of y = X - shift.  Bound per element of C: (n + 4) 2^-53 sum_i |y_ia y_ib|,
+    the worst case for any order of n rounded or fused products of once-rounded y; for t: (n + 4) 2^-53 sum_i |y_ia|.
+    A dropped or doubled row, tile or chunk exceeds either by many orders."""
+    _lib.require()
+    X, shift, rt, rC, at, aC = moment_case(d, n, shifted)
+    t, C = run_moments(torch.from_numpy(X).cuda(), shift, chunk_rows=chunk_rows)
+    t, C = t.cpu().numpy(), C.cpu().numpy()
+    assert (np.abs(C.astype(L) - rC) <= (n + 4) * U * aC).all()
+    assert (np.abs(t.astype(L) - rt) <= (n + 4) * U * at).all()
+    assert np.array_equal(C, C.T)
+
+
+@pytest.mark.parametrize("d", [16, 17, 129])
+def test_same_bits_for_every_grid_and_alignment(d):
+    _lib.require()
+    X, shift = moment_case(d, 200, True)[:2]
+    Xd = torch.from_numpy(X).cuda()
+    base = torch.empty(200 * d + 1, dtype=torch.float64, device="cuda")
+    off8 = base[1:].view(200, d)
+    off8.copy_(Xd)
+    assert Xd.data_ptr() % 16 == 0 and off8.data_ptr() % 16 == 8
+    t0, C0 = run_moments(Xd, shift, chunk_rows=64)
+    for rows, grid in ((Xd, 1), (Xd, 7), (Xd, 7), (off8, 0)):
+        t, C = run_moments(rows, shift, grid=grid, chunk_rows=64)
+        assert torch.equal(t, t0) and torch.equal(C, C0)
+
+
+@pytest.mark.parametrize("n", [1, 65, 200])
+@pytest.mark.parametrize("nx,k", [(1, 1), (17, 3), (128, 16), (129, 17), (1024, 5)])
+def test_projection_against_the_oracle(nx, k, n):
+    """P against the longdouble value; column 1 is dropped (scale 0) and holds NaN, column 2 passes through (mean 0,
+    scale 1).  Bound per score: (nx + 6) 2^-53 sum_c |z_ic T_jc| / sstd_j: the subtraction, the two divisions and any
+    order of nx fused products."""
+    _lib.require()
+    rng = np.random.default_rng(nx + n)
+    X = rng.standard_normal((n, nx)) + 2.0
+    mean, scale = rng.standard_normal(nx), rng.uniform(0.5, 2.0, nx)
+    T, sstd = rng.standard_normal((k, nx)), rng.uniform(0.5, 2.0, k)
+    Z = (X.astype(L) - mean.astype(L)) / scale.astype(L)
+    if nx >= 3:
+        X[:, 1], scale[1], Z[:, 1] = np.nan, 0.0, 0.0
+        mean[2], scale[2], Z[:, 2] = 0.0, 1.0, X[:, 2]
+    ref = Z @ T.T.astype(L) / sstd.astype(L)
+    bound = (nx + 6) * U * (np.abs(Z) @ np.abs(T.T).astype(L)) / sstd.astype(L)
+    calls = M.MOMENTS_CALLS
+    P = M.pca_project(torch.from_numpy(X).cuda(), mean, scale, T, sstd).cpu().numpy()
+    assert M.MOMENTS_CALLS > calls and P.shape == (n, k)
+    assert (np.abs(P.astype(L) - ref) <= bound).all()
+
+
+def err(a, b):
+    """Largest error of a against b, relative to b's largest entry."""
+    a, b = np.asarray(a, dtype=L), np.asarray(b, dtype=L)
+    return float(np.abs(a - b).max() / np.abs(b).max())
+
+
+def stats_of(S, mean, n):
+    """(corr, means, stddevs, cov) of the non-constant columns from the centred sums S."""
+    cov = S / (n - 1)
+    sd = np.sqrt(np.diagonal(cov))
+    return cov / np.outer(sd, sd), mean, sd, cov
+
+
+def test_operators_on_columns_of_a_large_mean(monkeypatch):
+    """CorrelationBatchOp and PcaTrainBatchOp on 200 x 5 device columns of mean 1e8 and unit spread (columns 0 and 1
+    correlated, column 4 constant) against the two-pass longdouble oracle.  Tolerance: 8 x the error of
+    ``moments_torch`` (fp64, CPU, the same shift and formulas) against that oracle, at least 2^-46.  Then both
+    operators on the same columns around mean 0 against ``ALINK_MOMENTS_HIP=0`` by the same tolerance, and
+    PcaPredictBatchOp of one model under both settings within the projection's bound."""
+    _lib.require()
+    from alink_amd import CorrelationBatchOp, MemSourceBatchOp, PcaPredictBatchOp, PcaTrainBatchOp, useLocalEnv
+    rng = np.random.default_rng(7)
+    E = rng.standard_normal((200, 5))
+    E[:, 1] = 0.8 * E[:, 0] + 0.6 * E[:, 1]
+    E[:, 4] = 0.0
+    names = ["a", "b", "c", "d", "e"]
+
+    def ops(X, flag):
+        monkeypatch.setenv("ALINK_MOMENTS_HIP", flag)
+        calls = M.MOMENTS_CALLS
+        src = MemSourceBatchOp([tuple(r) for r in X.tolist()], ", ".join(f"{c} double" for c in names))
+        corr = CorrelationBatchOp().setSelectedCols(names).linkFrom(src).collectCorrelation().getCorrelation()
+        model = PcaTrainBatchOp().setSelectedCols(names).setK(2).linkFrom(src)
+        m = next(json.loads(v) for r in model.collect() for v in r if isinstance(v, str) and '"idxNonEqual"' in v)
+        assert (M.MOMENTS_CALLS > calls) == (flag == "1")
+        return np.asarray(corr), m, model, src
+
+    def parts(corr, m):
+        assert m["idxNonEqual"] == [0, 1, 2, 3]
+        assert np.isnan(np.asarray(corr)[4, :4]).all()
+        return np.asarray(corr)[:4, :4], m["means"], m["stddevs"], m["cov"]
+    big, small = E + 1e8, E + np.array([0.0, 0.0, 0.0, 0.0, 3.0])
+    Xl = big[:, :4].astype(L)
+    ref = stats_of((Xl - Xl.mean(0)).T @ (Xl - Xl.mean(0)), Xl.mean(0), 200)
+    shift = torch.from_numpy(big[0, :4].copy())
+    t, C = M.moments_torch(torch.from_numpy(big[:, :4].copy()), shift)
+    cpu = stats_of((C - torch.outer(t, t) / 200).numpy(), (shift + t / 200).numpy(), 200)
+    tol = max(8 * max(err(a, b) for a, b in zip(cpu, ref)), 2.0 ** -46)
+    try:
+        useLocalEnv(1, device="cuda:0")
+        got = parts(*ops(big, "1")[:2])
+        new, old = ops(small, "1"), ops(small, "0")
+        scores = {}
+        for flag in ("1", "0"):
+            monkeypatch.setenv("ALINK_MOMENTS_HIP", flag)
+            rows = PcaPredictBatchOp().setPredictionCol("p").setReservedCols([]).linkFrom(old[2], old[3]).collect()
+            scores[flag] = np.array([[float(v) for v in r[0].split(" ")] for r in rows])
+    finally:
+        useLocalEnv(1, device="cpu")
+    errs = [err(a, b) for a, b in zip(got, ref)]
+    print("tol %.3e" % tol, "errors", errs)
+    assert np.isfinite(got[0]).all() and max(errs) <= tol
+    between = [err(a, b) for a, b in zip(parts(*new[:2]), parts(*old[:2]))]
+    print("against the former path", between)
+    assert max(between) <= tol
+    # CORR model, SIMPLE transform: z = x / std on the four kept columns, no score scaling
+    m = old[1]
+    Zt = np.abs(small[:, :4].astype(L) / np.asarray(m["stddevs"], dtype=L)) @ np.abs(np.asarray(m["coef"], dtype=L)).T
+    assert (np.abs(scores["1"].astype(L) - scores["0"].astype(L)) <= (5 + 6) * U * Zt).all()
