@@ -15,7 +15,8 @@ from typing import Optional
 
 import torch  # noqa: F401  (loads torch's HIP runtime first; our .so resolves libamdhip64.so.7 to it)
 
-__all__ = ["lib", "require", "available", "kernels_enabled", "sized_gate", "call", "query", "LIB_PATH", "stream_ptr"]
+__all__ = ["lib", "require", "available", "kernels_enabled", "sized_gate", "call", "query", "LIB_PATH", "stream_ptr",
+           "chunk_rows", "chunk_buffers"]
 
 LIB_PATH = os.environ.get("ALINK_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libalink_hip.so")
 _lib: Optional[ctypes.CDLL] = None
@@ -281,6 +282,22 @@ def sized_gate(flag: str, device, size, minimum: int) -> bool:
     if value != "1" and int(size() if callable(size) else size) < minimum:
         return False
     return kernels_enabled()
+
+
+def chunk_rows(n: int, partial_doubles: int, scratch_bytes: int, max_chunks: int, min_rows: int) -> int:
+    """Rows per chunk of a pass whose chunk partials (``partial_doubles`` fp64 each) are merged in chunk order, from
+    its arguments alone: at most ``max_chunks`` chunks and never more than fit ``scratch_bytes``, at least ``min_rows``
+    rows, a multiple of 64."""
+    nch = max(1, min(scratch_bytes // (8 * partial_doubles), max_chunks))
+    return max(min_rows, -(-(-(-n // nch)) // 64) * 64)
+
+
+def chunk_buffers(n: int, crows: int, partial_doubles: int, device):
+    """``(nchunk, part [nchunk, partial_doubles], out [partial_doubles])`` of such a pass over ``n`` rows in chunks
+    of ``crows``: fp64, uninitialised (the pass writes every entry that is read)."""
+    nchunk = -(-n // crows)
+    return (nchunk, torch.empty((nchunk, partial_doubles), dtype=torch.float64, device=device),
+            torch.empty(partial_doubles, dtype=torch.float64, device=device))
 
 
 def stream_ptr(device=None) -> int:

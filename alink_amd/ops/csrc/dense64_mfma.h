@@ -47,25 +47,6 @@ __device__ __forceinline__ d4_t mf64(double a, double b, d4_t c) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
 
-// upper tile t of an NT x NT tile matrix, tile rows ascending, then tile columns (the Gram kernels of glm.hip and
-// moments.hip deal these tiles to the waves)
-constexpr int tile_a(int nt, int t) {
-    int ta = 0;
-    while (t >= nt - ta) {
-        t -= nt - ta;
-        ++ta;
-    }
-    return ta;
-}
-constexpr int tile_b(int nt, int t) {
-    int ta = 0;
-    while (t >= nt - ta) {
-        t -= nt - ta;
-        ++ta;
-    }
-    return ta + t;
-}
-
 // the four lanes (lane & 15 fixed) that share a data row: both partners add the same two values at each step, so
 // every one of them ends with the same bits
 __device__ __forceinline__ double group_sum(double v) {
@@ -174,4 +155,18 @@ inline unsigned row_blocks(int64_t rows, int grid, int64_t dflt) {
         else if ((p) == P1) ALINK_D64_LAUNCH_VEC(KERNEL, P1, vec, blocks, st, __VA_ARGS__);                       \
         else if ((p) == P2) ALINK_D64_LAUNCH_VEC(KERNEL, P2, vec, blocks, st, __VA_ARGS__);                       \
         else ALINK_D64_LAUNCH_VEC(KERNEL, P3, vec, blocks, st, __VA_ARGS__);                                      \
+    } while (0)
+// The same for kernels that take every tile count nt = 1 .. 8 (glm.hip, moments.hip; the caller has checked the range).
+#define ALINK_D64_LAUNCH_NT8(KERNEL, nt, vec, blocks, st, ...)                                                     \
+    do {                                                                                                           \
+        switch (nt) {                                                                                              \
+            case 1: ALINK_D64_LAUNCH_VEC(KERNEL, 1, vec, blocks, st, __VA_ARGS__); break;                          \
+            case 2: ALINK_D64_LAUNCH_VEC(KERNEL, 2, vec, blocks, st, __VA_ARGS__); break;                          \
+            case 3: ALINK_D64_LAUNCH_VEC(KERNEL, 3, vec, blocks, st, __VA_ARGS__); break;                          \
+            case 4: ALINK_D64_LAUNCH_VEC(KERNEL, 4, vec, blocks, st, __VA_ARGS__); break;                          \
+            case 5: ALINK_D64_LAUNCH_VEC(KERNEL, 5, vec, blocks, st, __VA_ARGS__); break;                          \
+            case 6: ALINK_D64_LAUNCH_VEC(KERNEL, 6, vec, blocks, st, __VA_ARGS__); break;                          \
+            case 7: ALINK_D64_LAUNCH_VEC(KERNEL, 7, vec, blocks, st, __VA_ARGS__); break;                          \
+            default: ALINK_D64_LAUNCH_VEC(KERNEL, 8, vec, blocks, st, __VA_ARGS__); break;                         \
+        }                                                                                                          \
     } while (0)

@@ -10,15 +10,10 @@
 //           KA are zero.  Two xor steps add the four lanes, so eta has the same bits on every path.
 //   family  lane sub = 0 evaluates family and link (a wave-uniform switch on run-time ids) and writes z into the
 //           row's column k + 1 and ww beside the rows.
-//   Gram    after one barrier, v_mfma_f64_16x16x4_f64 over four consecutive rows per instruction:
-//           A[m][g] = ww_{i0+g} a_{i0+g}[16 ta + m], B[g][m] = a_{i0+g}[16 tb + m]; a lane reads its row's NT column
-//           values from LDS once per step.  Upper tile triangle only: tile t (ta ascending, then tb) belongs to wave
-//           t mod 4, at most 9 accumulator tiles per wave; with NT <= 2 (1 or 3 tiles) the waves split the batch's
-//           rows instead and their partials are added in wave order at the chunk's end.  The rule depends on k alone.
-//   merge   part [nchunk, 1 + KA KA] holds each chunk's sum ww^2 and the entries of its upper tiles; one lane per
-//           output element adds them in chunk order and mirrors the triangle.  No float atomics: the same bits for
-//           every grid and run.
-// The LDS row stride is 16 NT + 16 doubles, so the four lane groups of a Gram read start 32 banks apart.
+//   Gram    after one barrier, the weighted upper tile triangle of gram64_mfma.h (the operand maps, which wave owns
+//           which tile and the order of every addition are described there): at most 9 accumulator tiles per wave.
+//   merge   part [nchunk, 1 + KA KA] holds each chunk's sum ww^2 and the entries of its upper tiles, merged in chunk
+//           order by gram_merge_kernel: the same bits for every grid and run.
 //
 // alink_glm_rows_f64: the same row load and dot without the LDS staging, then by mask: pred (mu), eta, the four
 // residuals, z and ww, and per 64-row batch one partial of [deviance, deviance at unlink(cnull + off), pearson^2, w],
@@ -30,7 +25,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "dense64_mfma.h"
+#include "gram64_mfma.h"
 
 #pragma clang fp contract(off)
 
@@ -38,9 +33,6 @@ namespace {
 
 using d64::d2_t;
 using d64::d4_t;
-using d64::mf64;
-using d64::tile_a;
-using d64::tile_b;
 
 constexpr double EPSILON = 1e-16, DELTA = 0.1, JAVA_MAX_VALUE = 1.7976931348623157e308, JAVA_MIN_VALUE = 4.9e-324;
 constexpr int GLM_KMAX = 126;
@@ -216,53 +208,21 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// pc = the chunk's [sum ww^2 | G [ka, ka]]: acc[s][q] = G[16 ta + g + 4 q][16 tb + m] of slot s's tile
 template <int NT>
-struct Gram {
-    static constexpr int S = 16 * NT + 16;              // LDS row stride in doubles
-    static constexpr int T = NT * (NT + 1) / 2;         // upper tiles
-    static constexpr bool SPLIT = NT <= 2;              // the waves split the rows, not the tiles
-    static constexpr int MAXT = SPLIT ? T : (T + 3) / 4;   // accumulator tiles per wave
-
-    // slot s of wave WAVE
-    static constexpr int tile(int wave, int s) { return SPLIT ? s : wave + 4 * s; }
-
-    // one step of four rows: acc[s] += (ww a[ta]) a[tb]^T for the wave's slots s, the tile indices compile-time
+struct GramStore {
+    using G = d64::GramTiles<NT, true, false>;
     template <int WAVE, int s = 0>
-    static __device__ __forceinline__ void step(d4_t (&acc)[MAXT], double ww, const double (&v)[NT]) {
-        if constexpr (s < MAXT) {
-            constexpr int t = tile(WAVE, s);
-            if constexpr (t < T) acc[s] = mf64(ww * v[tile_a(NT, t)], v[tile_b(NT, t)], acc[s]);
-            step<WAVE, s + 1>(acc, ww, v);
-        }
-    }
-
-    // the products of the staged batch: all 64 rows for the wave's tiles, or the wave's 16 rows for every tile
-    template <int WAVE>
-    static __device__ __forceinline__ void batch(d4_t (&acc)[MAXT], const double* __restrict__ rows,
-                                                 const double* __restrict__ wws, int wave, int g, int m) {
-        const int base = SPLIT ? 16 * wave : 0;
-#pragma unroll 2
-        for (int r4 = 0; r4 < (SPLIT ? 4 : 16); ++r4) {
-            const int row = base + 4 * r4 + g;
-            const double ww = wws[row];
-            double v[NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) v[t] = rows[row * S + 16 * t + m];
-            step<WAVE>(acc, ww, v);
-        }
-    }
-
-    // acc[s][q] = G[16 ta + g + 4 q][16 tb + m] of slot s's tile
-    template <int WAVE, int s = 0>
-    static __device__ __forceinline__ void store(const d4_t (&acc)[MAXT], double* __restrict__ pc, int ka, int g,
+    static __device__ __forceinline__ void store(const d4_t (&acc)[G::MAXT], double* __restrict__ pc, int ka, int g,
                                                  int m) {
-        if constexpr (s < MAXT) {
-            constexpr int t = tile(WAVE, s);
-            if constexpr (t < T) {
-                const int cb = 16 * tile_b(NT, t) + m;
+        if constexpr (s < G::MAXT) {
+            constexpr int t = G::tile(WAVE, s);
+            if constexpr (t < G::TU) {
+                constexpr int ta = d64::tile_a(NT, t), tb = d64::tile_b(NT, t);
+                const int cb = 16 * tb + m;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const int ra = 16 * tile_a(NT, t) + g + 4 * q;
+                    const int ra = 16 * ta + g + 4 * q;
                     if (ra < ka && cb < ka) pc[1 + (int64_t)ra * ka + cb] = acc[s][q];
                 }
             }
@@ -271,17 +231,21 @@ struct Gram {
     }
 };
 
+// The second bound is waves per SIMD; with workgroups of 4 waves, one per SIMD, it is also workgroups per CU.  Two at
+// NT = 5: the LDS allows them at every NT <= 6 and the registers do up to NT = 4 unasked; at NT = 5 the compiler has to
+// be told, or it takes 244 + 32 registers and one (profiles/gram_shared_triangle.txt).  A compiler that chooses
+// otherwise may need another NT in the condition: the profile's table of occupancies is the check.
 template <int NT, bool VEC>
-__global__ __launch_bounds__(256) void glm_irls_kernel(
+__global__ __launch_bounds__(256, NT == 5 ? 2 : 1) void glm_irls_kernel(
         const double* __restrict__ X, const double* __restrict__ y, const double* __restrict__ w,
         const double* __restrict__ off, int64_t n, int k, const double* __restrict__ beta, double b0, Fl f, int mode,
         int64_t chunk_rows, int64_t nchunk, double* __restrict__ part) {
-    using G = Gram<NT>;
+    using G = d64::GramTiles<NT, true, false>;
     constexpr int S = G::S;
     __shared__ __attribute__((aligned(16))) double rows[64 * S];
     __shared__ __attribute__((aligned(16))) double bet[128];
     __shared__ double wws[64];
-    __shared__ __attribute__((aligned(32))) double red[G::SPLIT ? 4 * G::T * 256 : 1];
+    __shared__ __attribute__((aligned(32))) double red[G::RED];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = tid >> 2, sub = tid & 3;
@@ -324,65 +288,13 @@ __global__ __launch_bounds__(256) void glm_irls_kernel(
                 const double a = wws[lane];
                 sww += wave_sum(a * a);
             }
-            switch (wave) {
-                case 0: G::template batch<0>(acc, rows, wws, wave, g, m); break;
-                case 1: G::template batch<1>(acc, rows, wws, wave, g, m); break;
-                case 2: G::template batch<2>(acc, rows, wws, wave, g, m); break;
-                default: G::template batch<3>(acc, rows, wws, wave, g, m); break;
-            }
+            G::batch(acc, rows, wws, wave, g, m);
             __syncthreads();        // the batch's reads are done before the next one is staged
         }
         double* __restrict__ pc = part + c * P;
         if (tid == 0) pc[0] = sww;
-        if (G::SPLIT) {
-#pragma unroll
-            for (int s = 0; s < G::MAXT; ++s)
-                *reinterpret_cast<d4_t*>(red + ((wave * G::T + s) * 64 + lane) * 4) = acc[s];
-            __syncthreads();
-            if (wave == 0) {
-#pragma unroll
-                for (int s = 0; s < G::MAXT; ++s) {
-                    d4_t a = *reinterpret_cast<const d4_t*>(red + (s * 64 + lane) * 4);
-                    for (int ws = 1; ws < 4; ++ws) a += *reinterpret_cast<const d4_t*>(red + ((ws * G::T + s) * 64 + lane) * 4);
-                    acc[s] = a;
-                }
-                G::template store<0>(acc, pc, ka, g, m);
-            }
-            __syncthreads();
-        } else {
-            switch (wave) {
-                case 0: G::template store<0>(acc, pc, ka, g, m); break;
-                case 1: G::template store<1>(acc, pc, ka, g, m); break;
-                case 2: G::template store<2>(acc, pc, ka, g, m); break;
-                default: G::template store<3>(acc, pc, ka, g, m); break;
-            }
-        }
+        G::template finish<GramStore<NT>>(acc, red, wave, lane, pc, ka, g, m);
     }
-}
-
-// out [1 + ka ka] = [sum ww^2 | G]: every element the sum of its chunk partials in chunk order, the lower triangle
-// read from the upper
-__global__ __launch_bounds__(256) void glm_merge_kernel(int ka, int64_t nchunk, const double* __restrict__ part,
-                                                        double* __restrict__ out) {
-    const int64_t P = 1 + (int64_t)ka * ka;
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= P) return;
-    int64_t src = 0;
-    if (e > 0) {
-        const int a = (int)((e - 1) / ka), b = (int)((e - 1) - (int64_t)a * ka);
-        src = 1 + (a <= b ? (int64_t)a * ka + b : (int64_t)b * ka + a);
-    }
-    double s = part[src];
-    int64_t c = 1;
-    for (; c + 8 <= nchunk; c += 8) {       // eight loads in flight, added in chunk order
-        double t[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) t[u] = part[(c + u) * P + src];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += t[u];
-    }
-    for (; c < nchunk; ++c) s += part[c * P + src];
-    out[e] = s;
 }
 
 template <int NT, bool VEC>
@@ -480,20 +392,6 @@ bool ids_ok(int fam, int link, int mode) {
 
 }  // namespace
 
-#define ALINK_GLM_LAUNCH(KERNEL, nt, vec, blocks, st, ...)                                                         \
-    do {                                                                                                           \
-        switch (nt) {                                                                                              \
-            case 1: ALINK_D64_LAUNCH_VEC(KERNEL, 1, vec, blocks, st, __VA_ARGS__); break;                          \
-            case 2: ALINK_D64_LAUNCH_VEC(KERNEL, 2, vec, blocks, st, __VA_ARGS__); break;                          \
-            case 3: ALINK_D64_LAUNCH_VEC(KERNEL, 3, vec, blocks, st, __VA_ARGS__); break;                          \
-            case 4: ALINK_D64_LAUNCH_VEC(KERNEL, 4, vec, blocks, st, __VA_ARGS__); break;                          \
-            case 5: ALINK_D64_LAUNCH_VEC(KERNEL, 5, vec, blocks, st, __VA_ARGS__); break;                          \
-            case 6: ALINK_D64_LAUNCH_VEC(KERNEL, 6, vec, blocks, st, __VA_ARGS__); break;                          \
-            case 7: ALINK_D64_LAUNCH_VEC(KERNEL, 7, vec, blocks, st, __VA_ARGS__); break;                          \
-            default: ALINK_D64_LAUNCH_VEC(KERNEL, 8, vec, blocks, st, __VA_ARGS__); break;                         \
-        }                                                                                                          \
-    } while (0)
-
 extern "C" {
 
 // One IRLS statistics pass over X [n, k] (1 <= k <= 126), y, w, off [n]: out [1 + (k + 2)^2] = [sum ww^2 | G] through
@@ -511,10 +409,9 @@ int alink_glm_irls_f64(const double* X, const double* y, const double* w, const 
     const int ka = k + 2, nt = (ka + 15) / 16;
     const Fl f{fam, link, vp, lp};
     const unsigned blocks = (unsigned)(grid > 0 && grid < nchunk ? grid : nchunk);
-    ALINK_GLM_LAUNCH(glm_irls_kernel, nt, d64::vec_ok(k, X), blocks, st, X, y, w, off, n, k, beta, b0, f, mode,
-                     chunk_rows, nchunk, part);
-    const int64_t P = 1 + (int64_t)ka * ka;
-    hipLaunchKernelGGL(glm_merge_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, ka, nchunk, part, out);
+    ALINK_D64_LAUNCH_NT8(glm_irls_kernel, nt, d64::vec_ok(k, X), blocks, st, X, y, w, off, n, k, beta, b0, f, mode,
+                         chunk_rows, nchunk, part);
+    d64::gram_merge(1, ka, nchunk, part, out, st);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -535,8 +432,8 @@ int alink_glm_rows_f64(const double* X, const double* y, const double* w, const 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int nt = (k + 2 + 15) / 16;
     const Fl f{fam, link, vp, lp};
-    ALINK_GLM_LAUNCH(glm_rows_kernel, nt, d64::vec_ok(k, X), d64::row_blocks(n, grid, 8192), st, X, y, w, off, n, k,
-                     beta, b0, f, mode, mask, cnull, out, part);
+    ALINK_D64_LAUNCH_NT8(glm_rows_kernel, nt, d64::vec_ok(k, X), d64::row_blocks(n, grid, 8192), st, X, y, w, off, n,
+                         k, beta, b0, f, mode, mask, cnull, out, part);
     if (mask & M_SUMS) {
         const int64_t nb = (n + 63) / 64, nseg = (nb + GLM_SEG - 1) / GLM_SEG;
         double* segs = part + nb * 4;

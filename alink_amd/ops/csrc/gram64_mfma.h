@@ -1,0 +1,183 @@
+// The upper-triangle Gram tile deal shared by the fp64 Gram passes — glm.hip (the weighted Gram of the IRLS pass) and
+// moments.hip (the diagonal units of the moment pass) — gfx950 / MI355X.
+//
+// The problem they share: a workgroup of 4 waves has staged a batch of 64 rows a_i of NT tiles of 16 columns in LDS
+// (row stride S = 16 NT + 16 doubles, so the four lane groups of a read start 32 banks apart; the columns behind the
+// row's width are zero) and adds sum_i w_i a_i a_i^T to accumulators that stay in registers for a whole row chunk.
+//
+// Operand and result maps (one v_mfma_f64_16x16x4_f64 = four consecutive rows i0 .. i0 + 3, m = lane & 15,
+// g = lane >> 4):
+//   A[m][g] = a_{i0+g}[16 ta + m]   (WEIGHTED: times the row weight ww_{i0+g}, read from wws);
+//   B[g][m] = a_{i0+g}[16 tb + m];
+//   D  slot q = 0..3 of a lane is element [16 ta + g + 4 q][16 tb + m] of the sum.
+//   A lane reads its row's NT column values from LDS once per step and uses them for every tile it owns.
+// Tiles: the TU = NT (NT + 1) / 2 upper tiles in the order ta ascending, then tb (tile_a / tile_b); ONES: behind them
+// NT "ones" tiles, A = 1.0 on every lane, whose every result row is the column sum of tile tb (result row 0 is kept).
+//
+// Ownership, two rules:
+//   NT >= 3  tile t belongs to wave t mod 4, which runs all 64 rows of the batch for it;
+//   NT <= 2  (SPLIT) every wave holds all T tiles and runs its own 16 rows of the batch; at the chunk's end the four
+//            waves' partials are added through LDS (`red`) in wave order by wave 0, which stores them.
+// Both rules depend on the width (NT) alone: never on the grid, the chunk length or the row count, so a chunk's
+// partial has the same bits in every launch.  gram_merge_kernel then adds the chunks' partials in chunk order, one
+// lane per output element, and mirrors the lower triangle from the upper: no float atomics anywhere.
+//
+// The store of a wave's tiles at the chunk's end is the caller's: `finish` takes a type Store with
+//   template <int WAVE> static void store(const d4_t (&acc)[MAXT], Args... args)
+// and passes its trailing arguments on by value.  Store walks the wave's slots with tile() and writes slot q of a
+// tile by the result map above.  (An element hook `put(ra, cb, v)` under a shared store was tried first: it compiled
+// the guards of moments.hip to other code and the moment pass measured 0.2 % to 1 % slower at 96 and 128 columns,
+// profiles/gram_shared_triangle.txt.)
+//
+// No contraction: the pragma below covers this header's own code (the weight's multiply, the merge's additions) whatever
+// the including file says later; it stands here, before the first function, because a file-scope pragma holds from
+// where it is written and the including files set theirs only after their includes.
+#pragma once
+#include "dense64_mfma.h"
+
+#pragma clang fp contract(off)
+
+namespace d64 {
+
+// upper tile t of an NT x NT tile matrix, tile rows ascending, then tile columns
+constexpr int tile_a(int nt, int t) {
+    int ta = 0;
+    while (t >= nt - ta) {
+        t -= nt - ta;
+        ++ta;
+    }
+    return ta;
+}
+constexpr int tile_b(int nt, int t) {
+    int ta = 0;
+    while (t >= nt - ta) {
+        t -= nt - ta;
+        ++ta;
+    }
+    return ta + t;
+}
+
+template <int NT, bool WEIGHTED, bool ONES>
+struct GramTiles {
+    static constexpr int S = 16 * NT + 16;              // LDS row stride in doubles
+    static constexpr int TU = NT * (NT + 1) / 2;        // upper tiles
+    static constexpr int T = TU + (ONES ? NT : 0);      // and the ones tiles behind them
+    static constexpr bool SPLIT = NT <= 2;              // the waves split the rows, not the tiles
+    static constexpr int MAXT = SPLIT ? T : (T + 3) / 4;    // accumulator tiles per wave
+    static constexpr int RED = SPLIT ? 4 * T * 256 : 1;     // doubles of the LDS array `red` (32-byte aligned)
+
+    // slot s of wave WAVE
+    static constexpr int tile(int wave, int s) { return SPLIT ? s : wave + 4 * s; }
+
+    // one step of four rows for the wave's slots s, the tile indices compile-time
+    template <int WAVE, int s = 0>
+    static __device__ __forceinline__ void step(d4_t (&acc)[MAXT], double ww, const double (&v)[NT]) {
+        if constexpr (s < MAXT) {
+            constexpr int t = tile(WAVE, s);
+            // the tile's indices as constants of their own: left inside the call, their loops run on the device
+            constexpr int ta = t < TU ? tile_a(NT, t) : 0, tb = t < TU ? tile_b(NT, t) : t - TU;
+            if constexpr (t < TU && WEIGHTED) acc[s] = mf64(ww * v[ta], v[tb], acc[s]);
+            else if constexpr (t < TU) acc[s] = mf64(v[ta], v[tb], acc[s]);
+            else if constexpr (t < T) acc[s] = mf64(1.0, v[tb], acc[s]);
+            step<WAVE, s + 1>(acc, ww, v);
+        }
+    }
+
+    // the products of the staged batch: all 64 rows for the wave's tiles, or the wave's 16 rows for every tile
+    template <int WAVE>
+    static __device__ __forceinline__ void batch_of(d4_t (&acc)[MAXT], const double* __restrict__ rows,
+                                                    const double* __restrict__ wws, int wave, int g, int m) {
+        const int base = SPLIT ? 16 * wave : 0;
+#pragma unroll 2
+        for (int r4 = 0; r4 < (SPLIT ? 4 : 16); ++r4) {
+            const int row = base + 4 * r4 + g;
+            double ww = 0.0;
+            if constexpr (WEIGHTED) ww = wws[row];
+            double v[NT];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) v[t] = rows[row * S + 16 * t + m];
+            step<WAVE>(acc, ww, v);
+        }
+    }
+
+    // the batch staged in rows [64 * S] (and wws [64], read when WEIGHTED only) into the wave's accumulators; the
+    // caller's barriers stand before it (the batch is staged) and after it (its reads are done)
+    static __device__ __forceinline__ void batch(d4_t (&acc)[MAXT], const double* __restrict__ rows,
+                                                 const double* __restrict__ wws, int wave, int g, int m) {
+        switch (wave) {
+            case 0: batch_of<0>(acc, rows, wws, wave, g, m); break;
+            case 1: batch_of<1>(acc, rows, wws, wave, g, m); break;
+            case 2: batch_of<2>(acc, rows, wws, wave, g, m); break;
+            default: batch_of<3>(acc, rows, wws, wave, g, m); break;
+        }
+    }
+
+    // the end of a chunk: every thread of the workgroup calls it.  SPLIT: the four waves' partials through red
+    // [RED] in wave order, stored by wave 0 (two barriers, and a third so that red may be written again); else every
+    // wave stores its own tiles, Store::store<WAVE>(acc, args...).
+    template <class Store, class... Args>
+    static __device__ __forceinline__ void finish(d4_t (&acc)[MAXT], double* __restrict__ red, int wave, int lane,
+                                                  Args... args) {
+        if constexpr (SPLIT) {
+#pragma unroll
+            for (int s = 0; s < MAXT; ++s) *reinterpret_cast<d4_t*>(red + ((wave * T + s) * 64 + lane) * 4) = acc[s];
+            __syncthreads();
+            if (wave == 0) {
+#pragma unroll
+                for (int s = 0; s < MAXT; ++s) {
+                    d4_t a = *reinterpret_cast<const d4_t*>(red + (s * 64 + lane) * 4);
+                    for (int ws = 1; ws < 4; ++ws)
+                        a += *reinterpret_cast<const d4_t*>(red + ((ws * T + s) * 64 + lane) * 4);
+                    acc[s] = a;
+                }
+                Store::template store<0>(acc, args...);
+            }
+            __syncthreads();
+        } else {
+            switch (wave) {
+                case 0: Store::template store<0>(acc, args...); break;
+                case 1: Store::template store<1>(acc, args...); break;
+                case 2: Store::template store<2>(acc, args...); break;
+                default: Store::template store<3>(acc, args...); break;
+            }
+        }
+    }
+};
+
+namespace {         // a kernel of its own in every file that includes this header
+
+// part [nchunk, head + dim dim] -> out [head + dim dim]: every element the sum of its chunk partials in chunk order,
+// the lower triangle of the dim x dim matrix behind the `head` leading entries read from the upper
+__global__ __launch_bounds__(256) void gram_merge_kernel(int head, int dim, int64_t nchunk,
+                                                         const double* __restrict__ part, double* __restrict__ out) {
+    const int64_t P = head + (int64_t)dim * dim;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= P) return;
+    int64_t src = e;
+    if (e >= head) {
+        const int a = (int)((e - head) / dim), b = (int)((e - head) - (int64_t)a * dim);
+        src = head + (a <= b ? (int64_t)a * dim + b : (int64_t)b * dim + a);
+    }
+    double s = part[src];
+    int64_t c = 1;
+    for (; c + 8 <= nchunk; c += 8) {       // eight loads in flight, added in chunk order
+        double t[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) t[u] = part[(c + u) * P + src];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += t[u];
+    }
+    for (; c < nchunk; ++c) s += part[c * P + src];
+    out[e] = s;
+}
+
+// host side: its launch on stream st
+inline void gram_merge(int head, int dim, int64_t nchunk, const double* part, double* out, hipStream_t st) {
+    const int64_t P = head + (int64_t)dim * dim;
+    hipLaunchKernelGGL(gram_merge_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, head, dim, nchunk, part,
+                       out);
+}
+
+}  // namespace
+
+}  // namespace d64

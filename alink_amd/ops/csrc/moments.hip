@@ -10,22 +10,18 @@
 //           subtract the shift (staged once per unit in LDS) and store the shifted slice to the row's LDS slot; the
 //           columns behind d and the rows behind the chunk are zero.
 //   tiles   after one barrier, v_mfma_f64_16x16x4_f64 over four consecutive rows per instruction, with the operand
-//           and result maps of dense64_mfma.h: A[m][g] = y_{i0+g}[16 ta + m], B[g][m] = y_{i0+g}[16 tb + m], so
-//           slot q of a lane is C[16 ta + g + 4 q][16 tb + m].  Accumulators stay in registers for the whole chunk.
-//           diagonal unit (block of NT tiles): the NT (NT + 1) / 2 upper tiles (tile_a / tile_b order) and behind
-//             them NT "ones" tiles, A = 1.0 on every lane, whose every result row is the column sum t of tile tb:
-//             at most 36 + 8 tiles; tile t belongs to wave t mod 4.  With NT <= 2 (2 or 5 tiles) the waves split
-//             the batch's rows instead, and their partials are added in wave order at the chunk's end.
+//           and result maps of gram64_mfma.h.  Accumulators stay in registers for the whole chunk.
+//           diagonal unit (block of NT tiles): the upper tile triangle of gram64_mfma.h with its NT "ones" tiles,
+//             whose result is the column sum t: at most 36 + 8 tiles (which wave owns which is described there).
 //           off-diagonal unit (A < B, so A has 8 tiles, B has nb <= 8): wave w owns the tile rows 2 w and 2 w + 1
 //             and all nb tile columns, 16 tiles at most.
 //           Both rules depend on (d, A, B) alone, and t comes out of the matrix instruction: nothing depends on
 //           the grid.
-//   merge   part [nchunk, d + d d] holds each chunk's t and the entries of its upper tiles; one lane per output
-//           element adds them in chunk order and mirrors the triangle, so C is exactly symmetric.  No float atomics:
-//           the same bits for every grid and run.
+//   merge   part [nchunk, d + d d] holds each chunk's t and the entries of its upper tiles, merged in chunk order by
+//           gram_merge_kernel, which mirrors the triangle, so C is exactly symmetric: the same bits for every grid
+//           and run.
 // The diagonal units of the full blocks, the diagonal unit of a last block of fewer tiles and the off-diagonal units
 // are three launches (each kernel has its own tile count at compile time); they write disjoint parts of `part`.
-// The LDS row stride is 16 NT + 16 doubles, so the four lane groups of a tile read start 32 banks apart.
 //
 // alink_pca_project_f64: P[i, j] = sum_c z_ic T[j, c] / sstd[j], z_ic = (x_ic - mean[c]) / scale[c] (a true fp64
 // division; scale[c] = 0 gives exactly 0 whatever the cell holds), on the shared tile loop of dense64_mfma.h: 64
@@ -37,7 +33,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "dense64_mfma.h"
+#include "gram64_mfma.h"
 
 #pragma clang fp contract(off)
 
@@ -108,52 +104,17 @@ __device__ __forceinline__ void stage_shift(double* __restrict__ sh, const doubl
     if (t >= 0 && t < 16 * nt) sh[t] = (shift != nullptr && c0 + t < d) ? shift[c0 + t] : 0.0;
 }
 
+// pc = the chunk's [t | C], the block starts at column c0: the upper tiles' entries and, from result row 0 of a ones
+// tile, t
 template <int NT>
-struct Diag {
-    static constexpr int S = 16 * NT + 16;              // LDS row stride in doubles
-    static constexpr int TU = NT * (NT + 1) / 2;        // upper tiles
-    static constexpr int T = TU + NT;                   // and the ones tiles behind them
-    static constexpr bool SPLIT = NT <= 2;              // the waves split the rows, not the tiles
-    static constexpr int MAXT = SPLIT ? T : (T + 3) / 4;    // accumulator tiles per wave
-
-    // slot s of wave WAVE
-    static constexpr int tile(int wave, int s) { return SPLIT ? s : wave + 4 * s; }
-
-    // one step of four rows for the wave's slots s, the tile indices compile-time
+struct DiagStore {
+    using D = GramTiles<NT, false, true>;
     template <int WAVE, int s = 0>
-    static __device__ __forceinline__ void step(d4_t (&acc)[MAXT], const double (&v)[NT]) {
-        if constexpr (s < MAXT) {
-            constexpr int t = tile(WAVE, s);
-            // the tile's indices as constants of their own: left inside the call, their loops run on the device
-            constexpr int ta = t < TU ? tile_a(NT, t) : 0, tb = t < TU ? tile_b(NT, t) : t - TU;
-            if constexpr (t < TU) acc[s] = mf64(v[ta], v[tb], acc[s]);
-            else if constexpr (t < T) acc[s] = mf64(1.0, v[tb], acc[s]);
-            step<WAVE, s + 1>(acc, v);
-        }
-    }
-
-    // the products of the staged batch: all 64 rows for the wave's tiles, or the wave's 16 rows for every tile
-    template <int WAVE>
-    static __device__ __forceinline__ void batch(d4_t (&acc)[MAXT], const double* __restrict__ rows, int wave, int g,
-                                                 int m) {
-        const int base = SPLIT ? 16 * wave : 0;
-#pragma unroll 2
-        for (int r4 = 0; r4 < (SPLIT ? 4 : 16); ++r4) {
-            const int row = base + 4 * r4 + g;
-            double v[NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) v[t] = rows[row * S + 16 * t + m];
-            step<WAVE>(acc, v);
-        }
-    }
-
-    // pc = the chunk's [t | C]: the upper tiles' entries and, from result row 0 of a ones tile, t
-    template <int WAVE, int s = 0>
-    static __device__ __forceinline__ void store(const d4_t (&acc)[MAXT], double* __restrict__ pc, int d, int c0,
+    static __device__ __forceinline__ void store(const d4_t (&acc)[D::MAXT], double* __restrict__ pc, int d, int c0,
                                                  int g, int m) {
-        if constexpr (s < MAXT) {
-            constexpr int t = tile(WAVE, s);
-            if constexpr (t < TU) {
+        if constexpr (s < D::MAXT) {
+            constexpr int t = D::tile(WAVE, s);
+            if constexpr (t < D::TU) {
                 constexpr int ta = tile_a(NT, t), tb = tile_b(NT, t);
                 const int cb = c0 + 16 * tb + m;
 #pragma unroll
@@ -161,8 +122,8 @@ struct Diag {
                     const int ra = c0 + 16 * ta + g + 4 * q;
                     if (ra < d && cb < d) pc[d + (int64_t)ra * d + cb] = acc[s][q];
                 }
-            } else if constexpr (t < T) {
-                const int cb = c0 + 16 * (t - TU) + m;
+            } else if constexpr (t < D::T) {
+                const int cb = c0 + 16 * (t - D::TU) + m;
                 if (g == 0 && cb < d) pc[cb] = acc[s][0];
             }
             store<WAVE, s + 1>(acc, pc, d, c0, g, m);
@@ -176,11 +137,11 @@ __global__ __launch_bounds__(256) void moments_diag_kernel(const double* __restr
                                                            const double* __restrict__ shift, int blk0, int nblk,
                                                            int64_t chunk_rows, int64_t nchunk,
                                                            double* __restrict__ part) {
-    using D = Diag<NT>;
+    using D = GramTiles<NT, false, true>;
     constexpr int S = D::S;
     __shared__ __attribute__((aligned(32))) double rows[64 * S];
     __shared__ __attribute__((aligned(32))) double sh[16 * NT];
-    __shared__ __attribute__((aligned(32))) double red[D::SPLIT ? 4 * D::T * 256 : 1];
+    __shared__ __attribute__((aligned(32))) double red[D::RED];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = tid >> 2, sub = tid & 3;
@@ -203,39 +164,11 @@ __global__ __launch_bounds__(256) void moments_diag_kernel(const double* __restr
             load_slice<NT, VEC>(v, X + (ok ? i : r0) * (int64_t)d, ok, c0, d, sub);
             store_slice<NT>(rows + r * S, v, ok, c0, d, sh, sub);
             __syncthreads();
-            switch (wave) {
-                case 0: D::template batch<0>(acc, rows, wave, g, m); break;
-                case 1: D::template batch<1>(acc, rows, wave, g, m); break;
-                case 2: D::template batch<2>(acc, rows, wave, g, m); break;
-                default: D::template batch<3>(acc, rows, wave, g, m); break;
-            }
+            D::batch(acc, rows, nullptr, wave, g, m);
             __syncthreads();        // the batch's reads are done before the next one is staged
         }
         double* __restrict__ pc = part + c * P;
-        if (D::SPLIT) {
-#pragma unroll
-            for (int s = 0; s < D::MAXT; ++s)
-                *reinterpret_cast<d4_t*>(red + ((wave * D::T + s) * 64 + lane) * 4) = acc[s];
-            __syncthreads();
-            if (wave == 0) {
-#pragma unroll
-                for (int s = 0; s < D::MAXT; ++s) {
-                    d4_t a = *reinterpret_cast<const d4_t*>(red + (s * 64 + lane) * 4);
-                    for (int ws = 1; ws < 4; ++ws)
-                        a += *reinterpret_cast<const d4_t*>(red + ((ws * D::T + s) * 64 + lane) * 4);
-                    acc[s] = a;
-                }
-                D::template store<0>(acc, pc, d, c0, g, m);
-            }
-            __syncthreads();
-        } else {
-            switch (wave) {
-                case 0: D::template store<0>(acc, pc, d, c0, g, m); break;
-                case 1: D::template store<1>(acc, pc, d, c0, g, m); break;
-                case 2: D::template store<2>(acc, pc, d, c0, g, m); break;
-                default: D::template store<3>(acc, pc, d, c0, g, m); break;
-            }
-        }
+        D::template finish<DiagStore<NT>>(acc, red, wave, lane, pc, d, c0, g, m);
     }
 }
 
@@ -347,31 +280,6 @@ __global__ __launch_bounds__(256) void moments_off_kernel(const double* __restri
     }
 }
 
-// out [d + d d] = [t | C]: every element the sum of its chunk partials in chunk order, the lower triangle read from
-// the upper
-__global__ __launch_bounds__(256) void moments_merge_kernel(int d, int64_t nchunk, const double* __restrict__ part,
-                                                            double* __restrict__ out) {
-    const int64_t P = d + (int64_t)d * d;
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= P) return;
-    int64_t src = e;
-    if (e >= d) {
-        const int a = (int)((e - d) / d), b = (int)((e - d) - (int64_t)a * d);
-        src = d + (a <= b ? (int64_t)a * d + b : (int64_t)b * d + a);
-    }
-    double s = part[src];
-    int64_t c = 1;
-    for (; c + 8 <= nchunk; c += 8) {       // eight loads in flight, added in chunk order
-        double t[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) t[u] = part[(c + u) * P + src];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += t[u];
-    }
-    for (; c < nchunk; ++c) s += part[c * P + src];
-    out[e] = s;
-}
-
 // img: the image of T [k, nx] (dense64_mfma.h), nblk blocks of 16 NT table rows, ndch = ceil(nx / 32) dim chunks
 template <int NT, bool VEC>
 __global__ __launch_bounds__(64 * WAVES) void pca_project_kernel(
@@ -420,20 +328,6 @@ __global__ __launch_bounds__(64 * WAVES) void pca_project_kernel(
 
 }  // namespace
 
-#define ALINK_MOMENTS_DIAG(nt, vec, blocks, st, ...)                                                               \
-    do {                                                                                                           \
-        switch (nt) {                                                                                              \
-            case 1: ALINK_D64_LAUNCH_VEC(moments_diag_kernel, 1, vec, blocks, st, __VA_ARGS__); break;             \
-            case 2: ALINK_D64_LAUNCH_VEC(moments_diag_kernel, 2, vec, blocks, st, __VA_ARGS__); break;             \
-            case 3: ALINK_D64_LAUNCH_VEC(moments_diag_kernel, 3, vec, blocks, st, __VA_ARGS__); break;             \
-            case 4: ALINK_D64_LAUNCH_VEC(moments_diag_kernel, 4, vec, blocks, st, __VA_ARGS__); break;             \
-            case 5: ALINK_D64_LAUNCH_VEC(moments_diag_kernel, 5, vec, blocks, st, __VA_ARGS__); break;             \
-            case 6: ALINK_D64_LAUNCH_VEC(moments_diag_kernel, 6, vec, blocks, st, __VA_ARGS__); break;             \
-            case 7: ALINK_D64_LAUNCH_VEC(moments_diag_kernel, 7, vec, blocks, st, __VA_ARGS__); break;             \
-            default: ALINK_D64_LAUNCH_VEC(moments_diag_kernel, 8, vec, blocks, st, __VA_ARGS__); break;            \
-        }                                                                                                          \
-    } while (0)
-
 extern "C" {
 
 // One moment pass over X [n, d] (1 <= d <= 1024), shift [d] or null: out [d + d d] = [t | C] through
@@ -450,8 +344,11 @@ int alink_moments_f64(const double* X, int64_t n, int d, const double* shift, in
     const int nfull = d / MB, ntl = (d % MB + 15) / 16, nblk = nfull + (ntl > 0);
     auto blocks = [&](int64_t units) { return (unsigned)(grid > 0 && grid < units ? grid : units); };
     if (nfull > 0)
-        ALINK_MOMENTS_DIAG(8, vec, blocks(nchunk * nfull), st, X, n, d, shift, 0, nfull, crows, nchunk, part);
-    if (ntl > 0) ALINK_MOMENTS_DIAG(ntl, vec, blocks(nchunk), st, X, n, d, shift, nfull, 1, crows, nchunk, part);
+        ALINK_D64_LAUNCH_VEC(moments_diag_kernel, 8, vec, blocks(nchunk * nfull), st, X, n, d, shift, 0, nfull, crows,
+                             nchunk, part);
+    if (ntl > 0)
+        ALINK_D64_LAUNCH_NT8(moments_diag_kernel, ntl, vec, blocks(nchunk), st, X, n, d, shift, nfull, 1, crows, nchunk,
+                             part);
     if (nblk > 1) {
         const unsigned ob = blocks(nchunk * (nblk * (nblk - 1) / 2));
         if (vec)
@@ -461,9 +358,7 @@ int alink_moments_f64(const double* X, int64_t n, int d, const double* shift, in
             hipLaunchKernelGGL(moments_off_kernel<false>, dim3(ob), dim3(256), 0, st, X, n, d, shift, nblk, crows,
                                nchunk, part);
     }
-    const int64_t P = d + (int64_t)d * d;
-    hipLaunchKernelGGL(moments_merge_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, d, nchunk, part,
-                       out);
+    gram_merge(d, d, nchunk, part, out, st);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

@@ -62,10 +62,8 @@ def selected(X, fam: str, link: str) -> bool:
 
 
 def glm_chunk_rows(n: int, k: int) -> int:
-    """Rows per chunk of the IRLS pass, from (n, k) alone: at most ``GLM_CHUNKS`` chunks and never more than fit
-    ``GLM_SCRATCH_BYTES``, at least ``GLM_CHUNK_MIN_ROWS`` rows, a multiple of 64."""
-    nch = max(1, min(GLM_SCRATCH_BYTES // (8 * (1 + (k + 2) ** 2)), GLM_CHUNKS))
-    return max(GLM_CHUNK_MIN_ROWS, -(-(-(-n // nch)) // 64) * 64)
+    """Rows per chunk of the IRLS pass, from (n, k) alone: ``_lib.chunk_rows`` under the GLM constants."""
+    return _lib.chunk_rows(n, 1 + (k + 2) ** 2, GLM_SCRATCH_BYTES, GLM_CHUNKS, GLM_CHUNK_MIN_ROWS)
 
 
 def _family_link(fam, link, vp, lp):
@@ -154,10 +152,7 @@ def irls_stats(X, y, w, off, beta, intercept, fam, link, vp, lp, mode, grid: int
     _check(X, fam, link, (y, w, off))
     b = _beta(beta, k, dev) if mode == STEP else None
     crows = int(chunk_rows) if chunk_rows > 0 else glm_chunk_rows(n, k)
-    nchunk = -(-n // crows)
-    P = 1 + (k + 2) ** 2
-    part = torch.empty((nchunk, P), dtype=torch.float64, device=dev)
-    out = torch.empty(P, dtype=torch.float64, device=dev)
+    nchunk, part, out = _lib.chunk_buffers(n, crows, 1 + (k + 2) ** 2, dev)
     _lib.call("alink_glm_irls_f64", X.data_ptr(), y.data_ptr(), w.data_ptr(), off.data_ptr(), n, k,
               b.data_ptr() if b is not None else None, float(intercept), FAMILIES.index(fam), LINKS.index(link),
               float(vp), float(lp), int(mode), crows, nchunk, part.data_ptr(), out.data_ptr(), int(grid),

@@ -57,10 +57,8 @@ def selected(X) -> bool:
 
 
 def moments_chunk_rows(n: int, d: int) -> int:
-    """Rows per chunk of the moment pass, from (n, d) alone: at most ``MOMENTS_CHUNKS`` chunks and never more than
-    fit ``MOMENTS_SCRATCH_BYTES``, at least ``MOMENTS_CHUNK_MIN_ROWS`` rows, a multiple of 64."""
-    nch = max(1, min(MOMENTS_SCRATCH_BYTES // (8 * (d + d * d)), MOMENTS_CHUNKS))
-    return max(MOMENTS_CHUNK_MIN_ROWS, -(-(-(-n // nch)) // 64) * 64)
+    """Rows per chunk of the moment pass, from (n, d) alone: ``_lib.chunk_rows`` under the moment constants."""
+    return _lib.chunk_rows(n, d + d * d, MOMENTS_SCRATCH_BYTES, MOMENTS_CHUNKS, MOMENTS_CHUNK_MIN_ROWS)
 
 
 def moments_torch(X: torch.Tensor, shift: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -106,10 +104,7 @@ def moments(X: torch.Tensor, shift=None, grid: int = 0, chunk_rows: int = 0) -> 
         return torch.zeros(d, dtype=torch.float64, device=dev), torch.zeros((d, d), dtype=torch.float64, device=dev)
     sh = None if shift is None else _vec(shift, d, dev, "shift")
     crows = int(chunk_rows) if chunk_rows > 0 else moments_chunk_rows(n, d)
-    nchunk = -(-n // crows)
-    P = d + d * d
-    part = torch.empty((nchunk, P), dtype=torch.float64, device=dev)
-    out = torch.empty(P, dtype=torch.float64, device=dev)
+    nchunk, part, out = _lib.chunk_buffers(n, crows, d + d * d, dev)
     _lib.call("alink_moments_f64", X.data_ptr(), n, d, sh.data_ptr() if sh is not None else None, crows, nchunk,
               part.data_ptr(), out.data_ptr(), int(grid), _lib.stream_ptr(dev))
     MOMENTS_CALLS += 1

@@ -19,8 +19,10 @@ pytestmark = pytest.mark.gpu
 ALL = ("pred", "eta", "resid", "zw", "sums")
 COLS = ("eta", "pred", "z", "ww", "dres", "pres", "wres", "rres", "sums")
 KS, NS = (1, 2, 13, 14, 15, 30, 31, 126), (1, 3, 63, 64, 65, 200)
-# k and n taken in turn, and the widest rows over several chunks as well
-GRAM_CASES = list(zip(KS, itertools.cycle(NS))) + [(126, 200), (31, 65)]
+# k and n taken in turn, the widest rows over several chunks as well, and k + 2 = 48, 64, 65, 96, 112: 3 .. 7 tiles,
+# where the deal of the tiles to the waves (t mod 4) is ragged
+GRAM_CASES = list(zip(KS, itertools.cycle(NS))) + [(126, 200), (31, 65), (46, 65), (62, 200), (63, 64), (94, 65),
+                                                    (110, 200)]
 
 
 def dev_case(case):
@@ -121,7 +123,7 @@ def test_clamps(fam, lnk):
         np.testing.assert_allclose(got[c], old[c], rtol=128 * 2.0 ** -53, atol=0, err_msg=c)
 
 
-@pytest.mark.parametrize("n,k", [(200, 14), (200, 126), (65, 31)])
+@pytest.mark.parametrize("n,k", [(200, 14), (200, 126), (65, 31), (200, 62), (200, 94)])
 def test_same_bits_for_every_grid(n, k):
     _lib.require()
     case = H.make_case("poisson", "log", n, k, seed=n + k)

@@ -15,8 +15,11 @@ pytestmark = pytest.mark.gpu
 L = np.longdouble
 U = L(2) ** -53
 DS, NS = (1, 2, 15, 16, 17, 127, 128, 129, 257, 1024), (1, 3, 63, 64, 65, 200)
-# d and n taken in turn, and two and three blocks over several chunks as well
-CASES = list(zip(DS, itertools.cycle(NS))) + [(129, 200), (257, 200)]
+# d and n taken in turn, two and three blocks over several chunks as well, a last block of 3 .. 7 tiles, where the
+# deal of the tiles to the waves (t mod 4) is ragged, and 177: a full block, a last block of 4 tiles and the
+# off-diagonal unit between them
+CASES = list(zip(DS, itertools.cycle(NS))) + [(129, 200), (257, 200), (33, 65), (49, 200), (65, 64), (81, 65),
+                                               (97, 200), (177, 200)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -51,7 +54,7 @@ def test_moments_against_the_oracle(d, n, chunk_rows, shifted):
     assert np.array_equal(C, C.T)
 
 
-@pytest.mark.parametrize("d", [16, 17, 129])
+@pytest.mark.parametrize("d", [16, 17, 81, 129])
 def test_same_bits_for_every_grid_and_alignment(d):
     _lib.require()
     X, shift = moment_case(d, 200, True)[:2]
