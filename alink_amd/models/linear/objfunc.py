@@ -22,6 +22,7 @@ from typing import Optional, Tuple
 import torch
 
 from ...ops import softmax as softmax_ops
+from ...ops import softmax_fused
 from ..common.features import FeatureMatrix
 
 __all__ = ["LabeledData", "UnaryLossFunc", "LogLossFunc", "LogisticLossFunc", "SquareLossFunc", "HingeLossFunc",
@@ -370,7 +371,26 @@ class SoftmaxObjFunc(OptimObjFunc):
         lse = self._logsumexp1(eta)
         return torch.exp(eta - lse[:, None])
 
+    def _fused_rows(self, data, coef):
+        """The dense fp64 rows when the fused softmax passes (``ops/softmax_fused.py``) take this partition, else
+        None: sparse rows, fp32, k1 > 64, m > 1024 and ``ALINK_SOFTMAX_HIP=0`` keep the GEMM + K16 path."""
+        X = data.X.dense
+        if X is None or coef.dtype != torch.float64 or X.shape[1] * self.k1 != coef.shape[0] or \
+                data.y.dtype != torch.float64 or data.w.dtype != torch.float64 or \
+                not softmax_fused.selected(X, self.k1):
+            return None
+        return X
+
     def grad_sum(self, data, coef):
+        X = self._fused_rows(data, coef)
+        if X is not None:
+            W = coef.reshape(self.k1, -1)
+            y, w = data.y.contiguous(), data.w.contiguous()
+            if X.shape[1] <= softmax_fused.SOFTMAX_FUSED_GRAD_MAX_M:
+                # logits, softmax and R^T X from one read of X; G is [k1, m], the [k][featDim] layout
+                return softmax_fused.fused_grad(X, y, w, W)[0].reshape(-1)
+            # a wide m: R from the row pass (no eta block, no K16 launch), then the split-K X^T R
+            return data.X.rmm(softmax_fused.rows(X, y, w, W, ("R",))["R"]).T.reshape(-1)
         # K16: w * (softmax - onehot) in one fused pass over the logits (torch formulas on the CPU)
         R, _ = softmax_ops.softmax_grad(self._eta(data, coef), data.y, data.w)
         G = data.X.rmm(R, coef.shape[0] // self.k1)  # [m, k1]
@@ -392,6 +412,12 @@ class SoftmaxObjFunc(OptimObjFunc):
     def calc_search_values(self, data, coef, dirv, beta, num_step):
         if not len(data):
             return torch.zeros(num_step + 1, dtype=coef.dtype, device=coef.device)
+        X = self._fused_rows(data, coef) if num_step + 1 <= softmax_fused.SOFTMAX_FUSED_MAX_STEPS else None
+        if X is not None:
+            # both logit blocks and every trial step's loss in registers, from one read of X
+            return softmax_fused.search_losses(X, data.y.contiguous(), data.w.contiguous(),
+                                               coef.reshape(self.k1, -1), dirv.reshape(self.k1, -1), beta,
+                                               num_step + 1)
         # every trial step's loss from one read of the two logit blocks (K16 search epilogue)
         return softmax_ops.softmax_search(self._eta(data, coef), self._eta(data, dirv), data.y, data.w, beta,
                                           num_step + 1)
