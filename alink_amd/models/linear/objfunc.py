@@ -22,7 +22,7 @@ from typing import Optional, Tuple
 import torch
 
 from ...ops import softmax as softmax_ops
-from ...ops import softmax_fused
+from ...ops import softmax_csr, softmax_fused
 from ..common.features import FeatureMatrix
 
 __all__ = ["LabeledData", "UnaryLossFunc", "LogLossFunc", "LogisticLossFunc", "SquareLossFunc", "HingeLossFunc",
@@ -361,6 +361,11 @@ class SoftmaxObjFunc(OptimObjFunc):
         return torch.logsumexp(torch.cat([eta, z], 1), 1)
 
     def loss_per_sample(self, data, coef):
+        fm = self._csr_rows(data, coef)
+        if fm is not None:
+            # the rows' losses from the CSR row pass: no [nnz, k1] block (the callers weight them themselves)
+            return softmax_csr.rows(fm, data.y.contiguous(), data.w.contiguous(), coef.reshape(self.k1, -1),
+                                    ("row_loss",))["row_loss"]
         eta = self._eta(data, coef)
         yk = data.y.long()
         lin = torch.where(yk < self.k1, eta.gather(1, yk.clamp(max=self.k1 - 1)[:, None])[:, 0],
@@ -381,7 +386,22 @@ class SoftmaxObjFunc(OptimObjFunc):
             return None
         return X
 
+    def _csr_rows(self, data, coef):
+        """The sparse matrix when the CSR softmax passes (``ops/softmax_csr.py``) take this partition, else None:
+        dense rows, fp32, k1 > 64, the CPU and ``ALINK_SOFTMAX_HIP=0`` keep the ``mm`` / ``rmm`` path."""
+        fm = data.X
+        if fm.dense is not None or coef.dtype != torch.float64 or fm.ncols * self.k1 != coef.shape[0] or \
+                data.y.dtype != torch.float64 or data.w.dtype != torch.float64 or \
+                not softmax_csr.selected(fm, self.k1):
+            return None
+        return fm
+
     def grad_sum(self, data, coef):
+        fm = self._csr_rows(data, coef)
+        if fm is not None:
+            # R from one wave per CSR row, then X^T R through the CSC view in a fixed order: no float atomics
+            return softmax_csr.grad(fm, data.y.contiguous(), data.w.contiguous(),
+                                    coef.reshape(self.k1, -1))[0].reshape(-1)
         X = self._fused_rows(data, coef)
         if X is not None:
             W = coef.reshape(self.k1, -1)
@@ -412,6 +432,12 @@ class SoftmaxObjFunc(OptimObjFunc):
     def calc_search_values(self, data, coef, dirv, beta, num_step):
         if not len(data):
             return torch.zeros(num_step + 1, dtype=coef.dtype, device=coef.device)
+        fm = self._csr_rows(data, coef) if num_step + 1 <= softmax_csr.SOFTMAX_CSR_MAX_STEPS else None
+        if fm is not None:
+            # [W ; D] as one table, both logits of a class on its lane: every trial step's loss from one row read
+            return softmax_csr.search_losses(fm, data.y.contiguous(), data.w.contiguous(),
+                                             coef.reshape(self.k1, -1), dirv.reshape(self.k1, -1), beta,
+                                             num_step + 1)
         X = self._fused_rows(data, coef) if num_step + 1 <= softmax_fused.SOFTMAX_FUSED_MAX_STEPS else None
         if X is not None:
             # both logit blocks and every trial step's loss in registers, from one read of X

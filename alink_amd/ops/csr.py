@@ -1,9 +1,9 @@
 """The CSR call path of the HIP row kernels: what every wrapper over sparse rows checks and hands to the library.
 
 The rows are a sparse ``FeatureMatrix`` (``crow`` int64 ``[n+1]``, ``col`` int32 / int64, ``val`` fp64).  The kernels
-of ``csrc/kmeans_sparse.hip``, ``csrc/evalcluster.hip`` and ``csrc/bisecting.hip`` take them through the same six
-leading arguments (``row_args``); the two row kernels of ``csrc/csr_rows.h`` take their table transposed and padded
-to ``kp(k)`` columns (``padded_transpose``).
+of ``csrc/kmeans_sparse.hip``, ``csrc/evalcluster.hip``, ``csrc/bisecting.hip``, ``csrc/naive_bayes.hip`` and
+``csrc/softmax_csr.hip`` take them through the same six leading arguments (``row_args``); the row kernels on the walk
+of ``csrc/csr_rows.h`` take their table transposed and padded to ``kp(k)`` columns (``padded_transpose``).
 
 * ``supported(fm)`` / ``use_hip(fm)``: whether the kernels take this matrix, and whether it goes to them;
 * ``clipped(fm, d)``: the torch paths' form of the kernels' entry guard;
