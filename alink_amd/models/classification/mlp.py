@@ -9,9 +9,13 @@ training = the shared L-BFGS (``models/linear/optim.py``, 3 line-search steps as
 over the mean cross-entropy with optional L1/L2.  Model: meta ``{vectorCol, isVectorInput, layers,
 featureCols}`` + the weight ``DenseVector`` JSON + label rows.
 
-MI355X design: the whole partition is one ``[n, d]`` device matrix; forward/backward are GEMMs
-(rocBLAS/hipBLASLt) with fused elementwise sigmoid/softmax, the gradient comes from autograd on the flat
-weight vector, and the line search evaluates the loss for all step sizes with one batched forward each.
+MI355X design: the whole partition is one ``[n, d]`` device matrix.  From ``MLP_MIN_ROWS`` fp64 rows on, networks of
+up to three affine layers inside the limits of ``ops/mlp_fused.py`` take the fused kernels of
+``ops/csrc/mlp_fused.hip``: the gradient is one forward / backward pass on the fp64 matrix cores that reads X once,
+the line search evaluates every trial step in one forward row pass, and prediction takes probabilities and labels
+from the same row pass on the table's device.  Other shapes and small partitions on a GPU take the explicit backward
+pass of ``ops/mlp.py`` (library GEMMs with fused HIP epilogues) and one torch forward per trial step; CPU data takes
+autograd.
 """
 from __future__ import annotations
 
@@ -22,6 +26,7 @@ import numpy as np
 import torch
 
 from ...ops import mlp as mlp_ops
+from ...ops import mlp_fused
 from ...common.javafmt import gson_dumps, java_str
 from ...common.jrandom import JavaRandom
 from ...common.linalg import DenseVector
@@ -32,7 +37,7 @@ from ...common.table import Column, MTable
 from ...common.types import Types
 from ...parallel import comm
 from ..common.features import extract_features
-from ..linear.model import _recover_label
+from ..linear.model import _recover_label, label_column
 from ..linear.objfunc import LabeledData, OptimObjFunc
 from ..linear.optim import optimize
 
@@ -75,11 +80,38 @@ class MlpObjFunc(OptimObjFunc):
         idx = data.y.long()
         return -torch.log(P.gather(1, idx[:, None])[:, 0].clamp_min(1e-300))
 
+    def _fused_rows(self, data, coef, grad):
+        """The dense fp64 rows when the fused MLP passes (``ops/mlp_fused.py``) take this partition, else None: the
+        CPU, fp32, shapes outside ``shape_ok``, small partitions and ``ALINK_MLP_HIP=0`` keep the former paths."""
+        X = data.X.dense
+        if X is None or coef.dtype != torch.float64 or coef.shape[0] != weight_size(self.layers) or \
+                data.y.dtype != torch.float64 or data.w.dtype != torch.float64 or \
+                not mlp_fused.selected(X, self.layers, grad):
+            return None
+        return X
+
     def loss_per_sample(self, data, coef):
+        X = self._fused_rows(data, coef, False)
+        if X is not None:
+            return mlp_fused.rows(X, data.y.contiguous(), data.w.contiguous(), coef.detach().contiguous(),
+                                  self.layers, ("row_loss",))["row_loss"]
         with torch.no_grad():
             return self._ce(data, coef)
 
+    def calc_search_values(self, data, coef, dirv, beta, num_step):
+        X = self._fused_rows(data, coef, False) if len(data) and num_step + 1 <= mlp_fused.MLP_FUSED_MAX_STEPS \
+            else None
+        if X is not None:
+            # every trial step's weight set and loss from one forward row pass
+            return mlp_fused.search_losses(X, data.y.contiguous(), data.w.contiguous(), coef.detach().contiguous(),
+                                           dirv.contiguous(), self.layers, beta, num_step + 1)
+        return super().calc_search_values(data, coef, dirv, beta, num_step)
+
     def grad_sum(self, data, coef):
+        X = self._fused_rows(data, coef, True)
+        if X is not None:   # forward, backward and the weight Grams from one read of X
+            return mlp_fused.fused_grad(X, data.y.contiguous(), data.w.contiguous(), coef.detach().contiguous(),
+                                        self.layers)[0]
         X = data.X.to_dense()
         if mlp_ops.kernel_supported(X, self.layers):   # K17: explicit backprop, GEMMs + fused HIP epilogues
             return mlp_ops.mlp_grad(X, data.y, data.w, coef.detach(), self.layers)[0]
@@ -166,7 +198,40 @@ class MlpcModelMapper(RichModelMapper):
         mt = MTable.from_rows([tuple(row)], self.dataSchema)
         return [c.to_list()[0] for c in self._map_columns(mt)]
 
+    def _device_rows(self, mt):
+        """The feature rows on the table's device when its feature columns live on a GPU and the forward row pass
+        takes the shape, else None."""
+        names = [self.vcol] if self.vcol else list(self.fcols or [])
+        if not names or not mt.num_rows:
+            return None
+        vals = [mt.col(n).values for n in names]
+        vals = [v if isinstance(v, torch.Tensor) else getattr(v, "val", None) for v in vals]     # a sparse block: val
+        if not all(isinstance(v, torch.Tensor) and v.is_cuda for v in vals):
+            return None
+        dev = vals[0].device
+        fm = extract_features(mt, self.fcols if not self.vcol else None, self.vcol, dev)
+        if fm.is_sparse:
+            fm.set_ncols(self.layers[0])
+        X = fm.to_dense().double()
+        if X.shape[1] != self.layers[0]:
+            X = torch.nn.functional.pad(X, (0, max(0, self.layers[0] - X.shape[1])))[:, :self.layers[0]]
+        X = X.contiguous()
+        return X if mlp_fused.selected(X, self.layers, False) else None
+
     def _map_columns(self, mt):
+        X = self._device_rows(mt)
+        if X is not None:
+            # probabilities and the first-maximum label from the forward row pass on the table's device
+            zero = torch.zeros(X.shape[0], dtype=torch.float64, device=X.device)
+            res = mlp_fused.rows(X, zero, zero, self.w.to(X.device, torch.float64).contiguous(), self.layers,
+                                 ("P", "label"))
+            cols = [label_column(self.labels, res["label"].cpu().numpy(), self.helper.out_types[0])]
+            if self.detail_col:
+                P = res["P"].cpu().numpy()
+                cols.append(Column.from_values(
+                    [gson_dumps({java_str(self.labels[j]): float(p[j]) for j in range(len(self.labels))}) for p in P],
+                    Types.STRING))
+            return cols
         fm = extract_features(mt, self.fcols if not self.vcol else None, self.vcol, torch.device("cpu"))
         if fm.is_sparse:
             fm.set_ncols(self.layers[0])

@@ -209,6 +209,10 @@ _SIGNATURES = {
                                _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp],
     "alink_softmax_csr_grad": [_c_vp, _c_vp, _c_vp, _c_int, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp,
                                _c_vp, _c_vp, _c_vp, _c_int, _c_vp],
+    "alink_mlp_fused_grad_f64": [_c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_i64,
+                                 _c_i64, _c_vp, _c_vp, _c_int, _c_vp],
+    "alink_mlp_fused_rows_f64": [_c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_int,
+                                 _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp],
     "alink_moments_f64": [_c_vp, _c_i64, _c_int, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_int, _c_vp],
     "alink_pca_project_f64": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_int, _c_vp],
     "alink_sos_search_f64": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_int, _c_i64, _c_i64, _c_d, _c_vp, _c_vp,
