@@ -326,9 +326,15 @@ def _pearson_pairwise(X: torch.Tensor, valid: torch.Tensor) -> np.ndarray:
     values, all-reduced in one buffer: n_ij, sum x_i, sum x_i^2 (over the pair's rows), sum x_i x_j."""
     M = valid.to(X.dtype)
     A = torch.where(valid, X, torch.zeros_like(X))
-    d = X.shape[1]
     mom = torch.stack([tn_matmul(M, M), tn_matmul(A, M), tn_matmul(A * A, M), tn_matmul(A, A)])
     comm.all_reduce(mom, "sum")
+    return _corr_of_pairwise(mom)
+
+
+def _corr_of_pairwise(mom: torch.Tensor) -> np.ndarray:
+    """The correlations from the summed pairwise-complete moments ``[N | S | Q | P]``; a per-column shift of the
+    values leaves every term unchanged, so it serves the GEMM chain and ``ops.moments.pairwise_moments`` alike."""
+    d = mom.shape[1]
     N, Sx, Sxx, Sxy = mom[0], mom[1], mom[2], mom[3]
     Sy, Syy = Sx.T, Sxx.T
     num = N * Sxy - Sx * Sy
@@ -378,6 +384,13 @@ def correlation(mt: MTable, cols: Sequence[str], method: str = "PEARSON", device
     valid = ~torch.stack(nulls, 1)
     if _is_spearman(method):
         X = torch.stack([_rank_present_global(X[:, j], valid[:, j]) for j in range(X.shape[1])], 1)
+    if X.is_cuda:       # one masked moment pass around a shared shift: NaN marks the absent cells
+        Xn = torch.where(valid, X, torch.full_like(X, float("nan")))
+        shift = momops.pairwise_shift(Xn)
+        if shift is not None:
+            mom = momops.pairwise_moments(Xn, shift)
+            comm.all_reduce(mom, "sum")
+            return CorrelationResult(_corr_of_pairwise(mom), list(cols))
     return CorrelationResult(_pearson_pairwise(X, valid), list(cols))
 
 

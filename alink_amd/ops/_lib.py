@@ -214,6 +214,7 @@ _SIGNATURES = {
     "alink_mlp_fused_rows_f64": [_c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_int,
                                  _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp],
     "alink_moments_f64": [_c_vp, _c_i64, _c_int, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_int, _c_vp],
+    "alink_pairwise_moments_f64": [_c_vp, _c_i64, _c_int, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp, _c_int, _c_vp],
     "alink_pca_project_f64": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_int, _c_vp],
     "alink_sos_search_f64": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_int, _c_i64, _c_i64, _c_d, _c_vp, _c_vp,
                              _c_vp, _c_int, _c_vp],

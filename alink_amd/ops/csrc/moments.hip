@@ -29,6 +29,29 @@
 // transformed in registers right after the guarded load (load_shifted = load_group + shift_group, as the moment pass).  The epilogue
 // divides by sstd[j] and writes P [n, k] only.
 //
+// alink_pairwise_moments_f64: the pairwise-complete statistics of rows whose NaN cells are missing, out [4, d, d] =
+// [N | S | Q | P] with y_ia = x_ia - shift_a on present cells and m_ia the presence flag:
+//   N[a,b] = sum_i m_ia m_ib,  S[a,b] = sum_i y_ia m_ib,  Q[a,b] = sum_i y_ia^2 m_ib,  P[a,b] = sum_i y_ia y_ib m_ia m_ib
+// (S and Q are not symmetric).  The scheme of the moment pass with a tile plan of its own: blocks of PB = 64 columns
+// (4 tiles; a tile pair needs about six accumulator tiles here, not one), a unit is (row chunk, block pair A <= B).
+//   load    as above, but only y goes to LDS, one slice per block (41 KB, 82 KB in an off-diagonal unit), and NaN is
+//           kept as the missing marker: the columns behind d and the rows behind the chunk are staged as NaN.
+//   tiles   a lane reads its row's y of a tile once per four-row step and forms v = isnan(y) ? 0 : y, z = v v and
+//           k = isnan(y) ? 0 : 1 in registers; one matrix instruction per tile pair gives k^T k (N), v^T v (P),
+//           v^T k (S) and z^T k (Q).
+//           diagonal unit of NT tiles: the upper triangle for N and P, all NT^2 pairs for S and Q, 2 NT (NT + 1) / 2 +
+//             2 NT^2 tiles (52 at NT = 4, 4 at NT = 1);
+//           off-diagonal unit (A of 4 tiles, B of nb <= 4): N_AB, P_AB, S_AB = v_A^T k_B, S_BA = v_B^T k_A, Q_AB,
+//             Q_BA, 24 nb tiles (96 at nb = 4: 192 accumulator registers of a wave).
+//           One rule for every width: tile t of the unit's list belongs to wave t mod 4, which runs all 64 rows of a
+//           batch for it (at NT = 1 the four waves hold N, P, S and Q).  It depends on (d, A, B) alone.  No
+//           instantiation spills, so no deal was narrowed.
+//   merge   part [nchunk, 4 d d], merged in chunk order by pairwise_merge_kernel, which mirrors the lower triangles
+//           of N and P only: they are exactly symmetric, S and Q stay as computed; no float atomics, the same bits
+//           for every grid, run and alignment.
+// The diagonal units of the full blocks, of a ragged last block, the off-diagonal units between full blocks and those
+// against the last block are four launches; they write disjoint parts of `part`.
+//
 // All arithmetic is fp64, no contraction: the only fused operation is the matrix instruction.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -326,6 +349,228 @@ __global__ __launch_bounds__(64 * WAVES) void pca_project_kernel(
     }
 }
 
+// ---- the pairwise-complete moment pass ----
+
+constexpr int PB = 64;              // columns per block of the pairwise pass: 4 tiles (six accumulator families)
+
+// One accumulator tile: plane `fam` of out (0 N, 1 S, 2 Q, 3 P); the A operand is kind ka (0 k, 1 v, 2 z) of tile ta
+// of side sa (0 block A, 1 block B) and gives the result's rows, the B operand (kb, sb, tb) its columns.
+struct PwTile {
+    int fam, ka, sa, ta, kb, sb, tb;
+};
+
+// The tiles of a unit and their deal: tile t belongs to wave t mod 4, which runs all 64 rows of a batch for it.
+// Diagonal unit (OFF false, NB = NA): N's upper tiles, P's upper tiles, S's NA^2, Q's NA^2.  Off-diagonal unit
+// (NA = 4): the families N_AB, P_AB, S_AB, S_BA, Q_AB, Q_BA of 4 NB tiles each, tile rows of A ascending, then B's.
+template <int NA, int NB, bool OFF>
+struct PairTiles {
+    static constexpr int SA = 16 * NA + 16, SB = 16 * NB + 16;     // LDS row strides (the rule of gram64_mfma.h)
+    static constexpr int TU = NA * (NA + 1) / 2;
+    static constexpr int T = OFF ? 6 * NA * NB : 2 * TU + 2 * NA * NA;
+    static constexpr int MAXT = (T + 3) / 4;
+
+    static constexpr PwTile get(int t) {
+        if (OFF) {
+            const int f = t / (NA * NB), ta = t % (NA * NB) / NB, tb = t % NB;
+            switch (f) {
+                case 0: return {0, 0, 0, ta, 0, 1, tb};
+                case 1: return {3, 1, 0, ta, 1, 1, tb};
+                case 2: return {1, 1, 0, ta, 0, 1, tb};
+                case 3: return {1, 1, 1, tb, 0, 0, ta};
+                case 4: return {2, 2, 0, ta, 0, 1, tb};
+                default: return {2, 2, 1, tb, 0, 0, ta};
+            }
+        }
+        if (t < TU) return {0, 0, 0, tile_a(NA, t), 0, 0, tile_b(NA, t)};
+        t -= TU;
+        if (t < TU) return {3, 1, 0, tile_a(NA, t), 1, 0, tile_b(NA, t)};
+        t -= TU;
+        if (t < NA * NA) return {1, 1, 0, t / NA, 0, 0, t % NA};
+        t -= NA * NA;
+        return {2, 2, 0, t / NA, 0, 0, t % NA};
+    }
+
+    // one step of four rows for the wave's slots; o[side][kind][tile] are the lane's operands of the step
+    template <int WAVE, int s = 0>
+    static __device__ __forceinline__ void step(d4_t (&acc)[MAXT], const double (&o)[2][3][4]) {
+        if constexpr (s < MAXT) {
+            if constexpr (WAVE + 4 * s < T) {
+                constexpr PwTile p = get(WAVE + 4 * s);
+                acc[s] = mf64(o[p.sa][p.ka][p.ta], o[p.sb][p.kb][p.tb], acc[s]);
+            }
+            step<WAVE, s + 1>(acc, o);
+        }
+    }
+
+    // v, z and k of one side's NTS tiles from the staged y (NaN: missing); what the wave's tiles do not use is dropped
+    template <int NTS>
+    static __device__ __forceinline__ void operands(double (&o)[3][4], const double* __restrict__ yr, int m) {
+#pragma unroll
+        for (int t = 0; t < NTS; ++t) {
+            const double y = yr[16 * t + m];
+            const bool miss = y != y;
+            const double v = miss ? 0.0 : y;
+            o[0][t] = miss ? 0.0 : 1.0;
+            o[1][t] = v;
+            o[2][t] = v * v;
+        }
+    }
+
+    // the products of the staged batch for wave WAVE
+    template <int WAVE>
+    static __device__ __forceinline__ void batch_of(d4_t (&acc)[MAXT], const double* __restrict__ ra,
+                                                    const double* __restrict__ rb, int g, int m) {
+        for (int r4 = 0; r4 < 16; ++r4) {
+            const int row = 4 * r4 + g;
+            double o[2][3][4];
+            operands<NA>(o[0], ra + row * SA, m);
+            if constexpr (OFF) operands<NB>(o[1], rb + row * SB, m);
+            step<WAVE>(acc, o);
+        }
+    }
+
+    // the wave's tiles into the chunk's partial pc [4, d, d]; ca / cb the first columns of the two blocks
+    template <int WAVE, int s = 0>
+    static __device__ __forceinline__ void store(const d4_t (&acc)[MAXT], double* __restrict__ pc, int d, int ca,
+                                                 int cb, int g, int m) {
+        if constexpr (s < MAXT) {
+            if constexpr (WAVE + 4 * s < T) {
+                constexpr PwTile p = get(WAVE + 4 * s);
+                const int col = (p.sb ? cb : ca) + 16 * p.tb + m;
+                double* __restrict__ pf = pc + (int64_t)p.fam * d * d;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int row = (p.sa ? cb : ca) + 16 * p.ta + g + 4 * q;
+                    if (row < d && col < d) pf[(int64_t)row * d + col] = acc[s][q];
+                }
+            }
+            store<WAVE, s + 1>(acc, pc, d, ca, cb, g, m);
+        }
+    }
+};
+
+// store_slice with the missing marker: NaN where the row is not `ok` or the column is behind d; a NaN cell stays NaN
+// through the shift
+template <int NT>
+__device__ __forceinline__ void store_slice_nan(double* __restrict__ slot, const d4_t (&v)[NT], bool ok, int c0, int d,
+                                                const double* __restrict__ sh, int sub) {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int q = 4 * (4 * j + sub);
+        d4_t y = shift_group<false>(v[j], ok, c0 + q, d, sh, nullptr, q);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) y[s] = (ok && c0 + q + s < d) ? y[s] : __builtin_nan("");
+        *reinterpret_cast<d4_t*>(slot + q) = y;
+    }
+}
+
+// The units (chunk, pair) of one launch.  Diagonal (OFF false): pair = block blk0 + p, p < npair, of NA tiles.
+// Off-diagonal: A < B with A of 4 tiles and B of NB; last < 0: the pairs of the blocks 0 .. blk0 - 1 in the order A
+// ascending, then B (npair = blk0 (blk0 - 1) / 2); else B = last and A = p < npair.
+template <int NA, int NB, bool OFF, bool VEC>
+__device__ __forceinline__ void pairwise_units(const double* __restrict__ X, int64_t n, int d,
+                                               const double* __restrict__ shift, int blk0, int npair, int last,
+                                               int64_t chunk_rows, int64_t nchunk, double* __restrict__ part) {
+    using D = PairTiles<NA, NB, OFF>;
+    __shared__ __attribute__((aligned(32))) double ra[64 * D::SA];
+    __shared__ __attribute__((aligned(32))) double rb[OFF ? 64 * D::SB : 4];
+    __shared__ __attribute__((aligned(32))) double sh[2 * PB];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = tid >> 2, sub = tid & 3;
+    const int m = lane & 15, g = lane >> 4;
+    const int64_t P = 4 * (int64_t)d * d;
+    for (int64_t u = blockIdx.x; u < nchunk * npair; u += gridDim.x) {
+        const int64_t c = u / npair;
+        int p = (int)(u - c * npair), A = 0, B;
+        if (!OFF) {
+            A = B = blk0 + p;
+        } else if (last >= 0) {
+            A = p;
+            B = last;
+        } else {
+            while (p >= blk0 - 1 - A) {
+                p -= blk0 - 1 - A;
+                ++A;
+            }
+            B = A + 1 + p;
+        }
+        const int ca = A * PB, cb = B * PB;
+        const int64_t r0 = c * chunk_rows;
+        const int64_t r1 = r0 + chunk_rows < n ? r0 + chunk_rows : n;
+        stage_shift(sh, shift, ca, d, NA, tid);         // the previous unit's reads ended at its last barrier
+        if (OFF) stage_shift(sh + PB, shift, cb, d, NB, tid - PB);
+        __syncthreads();
+        d4_t acc[D::MAXT];
+#pragma unroll
+        for (int s = 0; s < D::MAXT; ++s) acc[s] = d4_t{0.0, 0.0, 0.0, 0.0};
+        for (int64_t bb = r0; bb < r1; bb += 64) {
+            const int64_t i = bb + r;
+            const bool ok = i < r1;
+            const double* __restrict__ xr = X + (ok ? i : r0) * (int64_t)d;
+            d4_t va[NA], vb[OFF ? NB : 1];
+            load_slice<NA, VEC>(va, xr, ok, ca, d, sub);
+            if constexpr (OFF) load_slice<NB, VEC>(vb, xr, ok, cb, d, sub);
+            store_slice_nan<NA>(ra + r * D::SA, va, ok, ca, d, sh, sub);
+            if constexpr (OFF) store_slice_nan<NB>(rb + r * D::SB, vb, ok, cb, d, sh + PB, sub);
+            __syncthreads();
+            switch (wave) {
+                case 0: D::template batch_of<0>(acc, ra, rb, g, m); break;
+                case 1: D::template batch_of<1>(acc, ra, rb, g, m); break;
+                case 2: D::template batch_of<2>(acc, ra, rb, g, m); break;
+                default: D::template batch_of<3>(acc, ra, rb, g, m); break;
+            }
+            __syncthreads();        // the batch's reads are done before the next one is staged
+        }
+        double* __restrict__ pc = part + c * P;
+        switch (wave) {
+            case 0: D::template store<0>(acc, pc, d, ca, cb, g, m); break;
+            case 1: D::template store<1>(acc, pc, d, ca, cb, g, m); break;
+            case 2: D::template store<2>(acc, pc, d, ca, cb, g, m); break;
+            default: D::template store<3>(acc, pc, d, ca, cb, g, m); break;
+        }
+    }
+}
+
+template <int NT, bool VEC>
+__global__ __launch_bounds__(256) void pairwise_diag_kernel(const double* __restrict__ X, int64_t n, int d,
+                                                            const double* __restrict__ shift, int blk0, int npair,
+                                                            int last, int64_t chunk_rows, int64_t nchunk,
+                                                            double* __restrict__ part) {
+    pairwise_units<NT, NT, false, VEC>(X, n, d, shift, blk0, npair, last, chunk_rows, nchunk, part);
+}
+
+template <int NB, bool VEC>
+__global__ __launch_bounds__(256) void pairwise_off_kernel(const double* __restrict__ X, int64_t n, int d,
+                                                           const double* __restrict__ shift, int blk0, int npair,
+                                                           int last, int64_t chunk_rows, int64_t nchunk,
+                                                           double* __restrict__ part) {
+    pairwise_units<4, NB, true, VEC>(X, n, d, shift, blk0, npair, last, chunk_rows, nchunk, part);
+}
+
+// part [nchunk, 4 d d] -> out [4, d, d]: every element the sum of its chunk partials in chunk order; the lower
+// triangles of N (plane 0) and P (plane 3) are read from the upper, S and Q are left as computed
+__global__ __launch_bounds__(256) void pairwise_merge_kernel(int d, int64_t nchunk, const double* __restrict__ part,
+                                                             double* __restrict__ out) {
+    const int64_t dd = (int64_t)d * d, P = 4 * dd;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= P) return;
+    const int f = (int)(e / dd);
+    const int a = (int)((e - f * dd) / d), b = (int)((e - f * dd) - (int64_t)a * d);
+    const int64_t src = ((f == 0 || f == 3) && a > b) ? f * dd + (int64_t)b * d + a : e;
+    double s = part[src];
+    int64_t c = 1;
+    for (; c + 8 <= nchunk; c += 8) {       // eight loads in flight, added in chunk order
+        double t[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) t[u] = part[(c + u) * P + src];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += t[u];
+    }
+    for (; c < nchunk; ++c) s += part[c * P + src];
+    out[e] = s;
+}
+
 }  // namespace
 
 extern "C" {
@@ -359,6 +604,38 @@ int alink_moments_f64(const double* X, int64_t n, int d, const double* shift, in
                                nchunk, part);
     }
     gram_merge(d, d, nchunk, part, out, st);
+    return hipGetLastError() == hipSuccess ? 0 : 2;
+}
+
+// One pairwise-complete moment pass over X [n, d] (1 <= d <= 1024; a NaN cell is missing), shift [d] or null:
+// out [4, d, d] = [N | S | Q | P] through nchunk = ceil(n / crows) row chunks (crows a multiple of 64) whose partials
+// part [nchunk, 4 d d] are merged in chunk order.  grid > 0 caps the workgroups of every launch; it changes no bit.
+int alink_pairwise_moments_f64(const double* X, int64_t n, int d, const double* shift, int64_t crows, int64_t nchunk,
+                               double* part, double* out, int grid, void* stream) {
+    if (n <= 0) return 0;
+    if (d < 1 || d > MOMENTS_DMAX || n >= (1ll << 31)) return 1;
+    if (crows < 64 || crows % 64 != 0 || nchunk != (n + crows - 1) / crows) return 1;
+    if (X == nullptr || part == nullptr || out == nullptr) return 1;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const bool vec = vec_ok(d, X);
+    const int nfull = d / PB, ntl = (d % PB + 15) / 16;
+    auto blocks = [&](int64_t units) { return (unsigned)(grid > 0 && grid < units ? grid : units); };
+    if (nfull > 0)
+        ALINK_D64_LAUNCH_VEC(pairwise_diag_kernel, 4, vec, blocks(nchunk * nfull), st, X, n, d, shift, 0, nfull, -1,
+                             crows, nchunk, part);
+    if (ntl > 0)
+        ALINK_D64_LAUNCH(pairwise_diag_kernel, ntl, 1, 2, 3, 4, vec, blocks(nchunk), st, X, n, d, shift, nfull, 1, -1,
+                         crows, nchunk, part);
+    if (nfull > 1) {
+        const int npair = nfull * (nfull - 1) / 2;
+        ALINK_D64_LAUNCH_VEC(pairwise_off_kernel, 4, vec, blocks(nchunk * npair), st, X, n, d, shift, nfull, npair, -1,
+                             crows, nchunk, part);
+    }
+    if (nfull > 0 && ntl > 0)
+        ALINK_D64_LAUNCH(pairwise_off_kernel, ntl, 1, 2, 3, 4, vec, blocks(nchunk * nfull), st, X, n, d, shift, nfull,
+                         nfull, nfull, crows, nchunk, part);
+    const int64_t P = 4 * (int64_t)d * d;
+    hipLaunchKernelGGL(pairwise_merge_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, d, nchunk, part, out);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

@@ -11,7 +11,13 @@
   / sstd[j]`` with true divisions; a column of ``scale`` 0 adds exactly nothing, whatever its cells hold;
 * ``moments_torch`` / ``pca_project_torch``: the same definitions in plain torch (CPU tensors take them);
 * ``shape_ok`` / ``supported`` / ``selected``: the shape rule, the rule on a GPU, and the gate
-  ``sized_gate("ALINK_MOMENTS_HIP", device, n, MOMENTS_MIN_ROWS)`` for widths up to ``MOMENTS_MAX_D``.
+  ``sized_gate("ALINK_MOMENTS_HIP", device, n, MOMENTS_MIN_ROWS)`` for widths up to ``MOMENTS_MAX_D``;
+* ``pairwise_moments(X, shift=None)`` -> ``out [4, d, d] = [N | S | Q | P]``, the pairwise-complete statistics of rows
+  whose NaN cells are missing: with ``y = x - shift`` on present cells and ``m`` the presence flag,
+  ``N[a,b] = sum_i m_ia m_ib``, ``S[a,b] = sum_i y_ia m_ib``, ``Q[a,b] = sum_i y_ia^2 m_ib`` and
+  ``P[a,b] = sum_i y_ia y_ib m_ia m_ib``: one masked pass on the fp64 matrix cores, ``N`` and ``P`` exactly
+  symmetric, the same bits for every launch and ``grid``; ``pairwise_moments_torch`` is the same in plain torch,
+  ``pairwise_selected`` the callers' gate and ``pairwise_shift`` the vote and the shift all ranks share.
 """
 from __future__ import annotations
 
@@ -24,7 +30,8 @@ from .kmeans_dense64 import centroid_image
 
 __all__ = ["MOMENTS_DMAX", "MOMENTS_MAX_D", "MOMENTS_MIN_ROWS", "MOMENTS_WIDE_MIN_ROWS", "MOMENTS_SCRATCH_BYTES", "shape_ok", "supported",
            "selected", "moments_chunk_rows", "moments", "moments_torch", "pca_project", "pca_project_torch",
-           "project_table", "shared_shift", "covariance"]
+           "project_table", "shared_shift", "covariance", "PAIRWISE_MIN_ROWS", "PAIRWISE_WIDE_MIN_ROWS",
+           "pairwise_moments", "pairwise_moments_torch", "pairwise_selected", "pairwise_shift"]
 
 MOMENTS_DMAX = 1024                 # widest row the kernels take
 MOMENTS_MAX_D = 1024                # widest row the callers send: the pass wins at every measured width (profiles/moments.txt)
@@ -34,6 +41,9 @@ MOMENTS_SCRATCH_BYTES = 256 << 20   # cap of the chunk partials [nchunk, d + d^2
 MOMENTS_CHUNKS = 512                # row chunks at most: the merge adds them one after another
 MOMENTS_CHUNK_MIN_ROWS = 256        # and no chunk shorter than this, so that a small n has few partials to merge
 MOMENTS_CALLS = 0                   # launches of the HIP moment / projection kernels (tests read it)
+PAIRWISE_MIN_ROWS = 1024            # pairwise pass, d <= 128: the former chain last wins at 256 x 128
+PAIRWISE_WIDE_MIN_ROWS = 65536      # d > 128: it wins at 16384 x 512 and 4096 x 1024 (profiles/pairwise_moments.txt)
+PAIRWISE_CALLS = 0                  # launches of the pairwise-complete moment pass (tests read it)
 
 
 def shape_ok(X) -> bool:
@@ -174,3 +184,69 @@ def covariance(X: torch.Tensor, shift: torch.Tensor):
     n = float(buf[0])
     t, C = buf[1:1 + d], buf[1 + d:].reshape(d, d)
     return n, shift + t / n, C - torch.outer(t, t) / n
+
+
+def pairwise_moments_torch(X: torch.Tensor, shift: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``pairwise_moments`` in plain torch: the presence mask, the shifted values with 0 in the missing cells, three
+    products with the mask and one of the values."""
+    M = (~torch.isnan(X)).to(X.dtype)
+    Y = X if shift is None else X - shift.to(device=X.device, dtype=X.dtype)[None, :]
+    A = torch.where(torch.isnan(X), torch.zeros_like(X), Y)
+    return torch.stack([M.T @ M, A.T @ M, (A * A).T @ M, A.T @ A])
+
+
+def pairwise_selected(X) -> bool:
+    """The callers' rule for the pairwise-complete pass: ``supported`` rows from ``PAIRWISE_MIN_ROWS`` rows on
+    (``PAIRWISE_WIDE_MIN_ROWS`` above 128 columns; ``ALINK_MOMENTS_HIP=1``: always, ``=0``: never); then the
+    project's fall-back rule."""
+    return supported(X) and _lib.sized_gate("ALINK_MOMENTS_HIP", X.device, X.shape[0],
+                                            PAIRWISE_MIN_ROWS if X.shape[1] <= 128 else PAIRWISE_WIDE_MIN_ROWS)
+
+
+def pairwise_moments(X: torch.Tensor, shift=None, grid: int = 0, chunk_rows: int = 0) -> torch.Tensor:
+    """``out [4, d, d] = [N | S | Q | P]`` of the module text for rows whose NaN cells are missing, shifted by
+    ``shift`` ([d] or None: zero).  On the GPU the same bits for every launch and every ``grid`` (``chunk_rows``, a
+    multiple of 64, overrides the chunk length, which otherwise follows from (n, d) alone).  CPU tensors take
+    ``pairwise_moments_torch``; GPU rows outside ``supported`` are an error (ask ``pairwise_selected`` first)."""
+    global PAIRWISE_CALLS
+    if not X.is_cuda:
+        return pairwise_moments_torch(X, None if shift is None else torch.as_tensor(shift, dtype=X.dtype))
+    _check(X)
+    n, d = X.shape
+    dev = X.device
+    if n == 0:          # nothing is launched for an empty partition
+        return torch.zeros((4, d, d), dtype=torch.float64, device=dev)
+    sh = None if shift is None else _vec(shift, d, dev, "shift")
+    crows = int(chunk_rows) if chunk_rows > 0 else _lib.chunk_rows(n, 4 * d * d, MOMENTS_SCRATCH_BYTES,
+                                                                   MOMENTS_CHUNKS, MOMENTS_CHUNK_MIN_ROWS)
+    nchunk, part, out = _lib.chunk_buffers(n, crows, 4 * d * d, dev)
+    _lib.call("alink_pairwise_moments_f64", X.data_ptr(), n, d, sh.data_ptr() if sh is not None else None, crows,
+              nchunk, part.data_ptr(), out.data_ptr(), int(grid), _lib.stream_ptr(dev))
+    PAIRWISE_CALLS += 1
+    return out.view(4, d, d)
+
+
+def pairwise_shift(X: torch.Tensor) -> Optional[torch.Tensor]:
+    """The vote and the shift of the pairwise-complete pass in one small ``all_gather_object``, as ``shared_shift``:
+    None when the pass is not taken (off a GPU or with ``ALINK_MOMENTS_HIP=0`` nothing is gathered; one rank's ``no``
+    keeps all ranks on the former path; a rank without rows votes by its shape), else per column the first present
+    finite value among the first 64 rows of the lowest rank that has one, else 0: near the column's values at the
+    cost of no pass over X.  fp64 [d] on the rows' device."""
+    from ..parallel import comm
+    if not _lib.sized_gate("ALINK_MOMENTS_HIP", X.device, PAIRWISE_MIN_ROWS, PAIRWISE_MIN_ROWS):
+        return None
+    n, d = X.shape
+    vote = pairwise_selected(X) if n else supported(X)
+    got = comm.all_gather_object((bool(vote), X[:64].tolist() if n and vote else None))
+    if not all(v for v, _ in got):
+        return None
+    sh = torch.zeros(d, dtype=torch.float64)
+    todo = torch.ones(d, dtype=torch.bool)
+    for rows in (r for _, r in got if r is not None):
+        H = torch.tensor(rows, dtype=torch.float64).reshape(-1, d)
+        fin = torch.isfinite(H)
+        first = fin.to(torch.int8).argmax(0)
+        take = todo & fin.any(0)
+        sh = torch.where(take, H[first, torch.arange(d)], sh)
+        todo &= ~take
+    return sh.to(X.device)
