@@ -11,7 +11,8 @@ mkdir -p variants
 build_var() {
   name=$1; flags=$2; d=build/variants/$name
   mkdir -p "$d"
-  cp alink_amd/ops/csrc/kmeans_v10.hip alink_amd/ops/csrc/kmeans_tile.h alink_amd/ops/csrc/kmeans_v10_body.h "$d/"
+  cp alink_amd/ops/csrc/kmeans_v10.hip alink_amd/ops/csrc/kmeans_tile.h alink_amd/ops/csrc/kmeans_v10_body.h \
+     alink_amd/ops/csrc/kmeans_v10_map.h "$d/"
   (cd "$d" && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mcode-object-version=5 $flags \
       -c kmeans_v10.hip -o kmeans_v10.o)
   objs=$(ls build/hip/*.o | grep -v kmeans_v10)
