@@ -21,6 +21,7 @@ from typing import Optional, Tuple
 
 import torch
 
+from ...ops import newton as newton_ops
 from ...ops import softmax as softmax_ops
 from ...ops import softmax_csr, softmax_fused
 from ..common.features import FeatureMatrix
@@ -252,13 +253,38 @@ class OptimObjFunc:
             f += self.l2 * float((coef * coef).sum().item())
         return f, ws
 
+    def _newton_sums(self, data: LabeledData, coef: torch.Tensor):
+        """``(hessian_sum, grad_sum, weightSum, lossSum)`` from one fused pass over the rows (``ops/newton.py``), or
+        None where the objective or the partition has none: the three separate calls then."""
+        return None
+
+    def _newton_rows(self, data: LabeledData, coef: torch.Tensor):
+        """The dense fp64 rows when the fused Newton pass takes this partition, else None: sparse rows, fp32,
+        non-contiguous rows, more than 128 coefficients, the CPU, ``ALINK_NEWTON_HIP=0`` and partitions below
+        ``NEWTON_MIN_ROWS`` keep ``hessian_sum`` / ``grad_sum`` / ``loss_per_sample``."""
+        X = data.X.dense
+        if X is None or coef.dtype != torch.float64 or data.y.dtype != torch.float64 or \
+                data.w.dtype != torch.float64 or not newton_ops.selected(X, coef.shape[0]):
+            return None
+        return X
+
+    @staticmethod
+    def _newton_pass(X, data, coef, code, param):
+        H, g, ws, loss = newton_ops.unary_sums(X, data.y.contiguous(), data.w.contiguous(), coef.contiguous(), code,
+                                               param)
+        ws, loss = torch.stack([ws, loss]).tolist()     # one copy to the host for both sums
+        return H, g, ws, loss
+
     def calc_hessian_gradient_loss(self, data: LabeledData, coef: torch.Tensor):
         """(hessian_sum, grad_sum, weightSum, lossSum) with L1/L2 scaled by the weight sum."""
         if not self.has_second_derivative():
             raise NotImplementedError("loss function can't support second derivative, newton precondition can "
                                       "not work.")
         d = coef.shape[0]
-        if len(data):
+        fused = self._newton_sums(data, coef) if len(data) else None
+        if fused is not None:
+            H, g, ws, loss = fused
+        elif len(data):
             H = self.hessian_sum(data, coef)
             g = self.grad_sum(data, coef)
             ws = float(self.sample_weight(data).sum().item())
@@ -323,6 +349,15 @@ class UnaryLossObjFunc(OptimObjFunc):
     def hessian_sum(self, data, coef):
         eta = data.X.mv(coef)
         return data.X.gram(self.unary.second_derivative(eta, data.y) * data.w, coef.shape[0])
+
+    def _newton_sums(self, data, coef):
+        from ...ops import linear as lops
+        code = lops.loss_code(self.unary)
+        X = self._newton_rows(data, coef) if code is not None else None
+        if X is None or X.shape[1] != coef.shape[0]:
+            return None
+        # eta, l, l', l'' and the weighted Gram from one read of X
+        return self._newton_pass(X, data, coef, code[0], code[1])
 
     def calc_search_values(self, data, coef, dirv, beta, num_step):
         if not len(data):
@@ -429,6 +464,18 @@ class SoftmaxObjFunc(OptimObjFunc):
                     H[t * m:(t + 1) * m, s * m:(s + 1) * m] = blk.T
         return H
 
+    def _newton_sums(self, data, coef):
+        X = data.X.dense
+        if X is None or coef.dtype != torch.float64 or X.shape[1] * self.k1 != coef.shape[0] or \
+                data.y.dtype != torch.float64 or data.w.dtype != torch.float64 or \
+                not newton_ops.selected(X, X.shape[1], self.k1):
+            return None
+        # every block (s, t) of the Hessian, G and both sums from one launch: no phi block, no copy of X
+        H, G, ws, loss = newton_ops.softmax_sums(X, data.y.contiguous(), data.w.contiguous(),
+                                                 coef.reshape(self.k1, -1).contiguous())
+        ws, loss = torch.stack([ws, loss]).tolist()
+        return H, G.reshape(-1), ws, loss
+
     def calc_search_values(self, data, coef, dirv, beta, num_step):
         if not len(data):
             return torch.zeros(num_step + 1, dtype=coef.dtype, device=coef.device)
@@ -487,3 +534,10 @@ class AftRegObjFunc(OptimObjFunc):
         H = data.X.gram(torch.exp(eps) / (sigma * sigma), d).clone()
         H[d - 1, d - 1] += (eps * (torch.exp(eps) * (1 + eps) - data.w)).sum()
         return H
+
+    def _newton_sums(self, data, coef):
+        X = self._newton_rows(data, coef)
+        if X is None or X.shape[1] + 1 != coef.shape[0]:
+            return None
+        # eps, the three coefficients and the two corner sums from one read of X; log sigma is read on the device
+        return self._newton_pass(X, data, coef, newton_ops.AFT, 0.0)

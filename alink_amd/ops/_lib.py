@@ -201,6 +201,10 @@ _SIGNATURES = {
                            _c_i64, _c_i64, _c_vp, _c_vp, _c_int, _c_vp],
     "alink_glm_rows_f64": [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_vp, _c_d, _c_int, _c_int, _c_d, _c_d, _c_int,
                            _c_int, _c_d, _c_vp, _c_vp, _c_vp, _c_int, _c_vp],
+    "alink_newton_unary_f64": [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_int, _c_d, _c_i64, _c_i64, _c_vp, _c_vp,
+                               _c_int, _c_vp],
+    "alink_newton_softmax_f64": [_c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp,
+                                 _c_int, _c_vp],
     "alink_softmax_fused_grad_f64": [_c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp,
                                      _c_int, _c_vp],
     "alink_softmax_fused_rows_f64": [_c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_int, _c_int, _c_d, _c_int,

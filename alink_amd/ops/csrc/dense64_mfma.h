@@ -32,6 +32,7 @@
 // and walks tiles, not chunks.  It shares the maps above, load_chunk, mf64 and group_sum, not stage / mfma_group.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 namespace d64 {
@@ -53,6 +54,35 @@ __device__ __forceinline__ double group_sum(double v) {
     v += __shfl_xor(v, 16, 64);
     v += __shfl_xor(v, 32, 64);
     return v;
+}
+
+__device__ __forceinline__ double group_max(double v) {
+    v = fmax(v, __shfl_xor(v, 16, 64));
+    v = fmax(v, __shfl_xor(v, 32, 64));
+    return v;
+}
+
+// log(1 + sum_c exp(e_c)) of one row from a lane's logits e[t][q] = class 16 t + g + 4 q (classes >= k1 are padding);
+// the four lanes of a row return the same bits
+template <int T>
+__device__ __forceinline__ double row_lse(const d4_t* e, int k1, int g) {
+    double mx = 0.0;        // the pivot's logit
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (16 * t + g + 4 * q < k1) mx = fmax(mx, e[t][q]);
+    }
+    mx = group_max(mx);
+    double se = 0.0;
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (16 * t + g + 4 * q < k1) se += exp(e[t][q] - mx);
+    }
+    se = group_sum(se) + exp(0.0 - mx);
+    return mx + log(se);
 }
 
 // The four dims j0 .. j0 + 3 of one row, zero outside [0, d) or when the row is not `ok`; no address is formed that

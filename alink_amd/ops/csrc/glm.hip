@@ -33,6 +33,8 @@ namespace {
 
 using d64::d2_t;
 using d64::d4_t;
+using d64::row_dot;
+using d64::stage_beta;
 
 constexpr double EPSILON = 1e-16, DELTA = 0.1, JAVA_MAX_VALUE = 1.7976931348623157e308, JAVA_MIN_VALUE = 4.9e-324;
 constexpr int GLM_KMAX = 126;
@@ -162,44 +164,6 @@ __device__ __forceinline__ void f_working(const Fl& f, int mode, double eta, dou
         z = y - o;
         ww = w;
     }
-}
-
-// The row xr [k] as seen by lane sub of its four lanes: v[j] = the columns 8 j + 2 sub and + 1 (zero behind k or
-// when the row is not `ok`; no address is loaded that lies outside the row), and the row's dot with bet (LDS, zero
-// behind k): every lane adds its pairs by fma in ascending j, then the four lanes are added by two xor steps, so
-// all four return the same bits, which depend on the row and k alone.
-template <int NT, bool VEC>
-__device__ __forceinline__ double row_dot(const double* __restrict__ xr, bool ok, int k, int sub,
-                                          const double* __restrict__ bet, d2_t (&v)[2 * NT]) {
-#pragma unroll
-    for (int j = 0; j < 2 * NT; ++j) {
-        const int c = 8 * j + 2 * sub;
-        d2_t t = {0.0, 0.0};
-        if (VEC) {
-            if (ok && c < k) t = *reinterpret_cast<const d2_t*>(xr + c);
-        } else {
-            if (ok && c < k) t[0] = xr[c];
-            if (ok && c + 1 < k) t[1] = xr[c + 1];
-        }
-        v[j] = t;
-    }
-    double dot = 0.0;
-#pragma unroll
-    for (int j = 0; j < 2 * NT; ++j) {
-        const d2_t b = *reinterpret_cast<const d2_t*>(bet + 8 * j + 2 * sub);
-        dot = fma(v[j][0], b[0], dot);
-        dot = fma(v[j][1], b[1], dot);
-    }
-    dot += __shfl_xor(dot, 1, 64);
-    dot += __shfl_xor(dot, 2, 64);
-    return dot;
-}
-
-// beta [k] into bet [128], zero behind k (or everywhere without a beta); every thread of the workgroup calls it
-__device__ __forceinline__ void stage_beta(double* __restrict__ bet, const double* __restrict__ beta, int k) {
-    const int tid = threadIdx.x;
-    if (tid < 128) bet[tid] = (beta != nullptr && tid < k) ? beta[tid] : 0.0;
-    __syncthreads();
 }
 
 __device__ __forceinline__ double wave_sum(double v) {

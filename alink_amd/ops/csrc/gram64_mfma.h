@@ -1,5 +1,6 @@
-// The upper-triangle Gram tile deal shared by the fp64 Gram passes — glm.hip (the weighted Gram of the IRLS pass) and
-// moments.hip (the diagonal units of the moment pass) — gfx950 / MI355X.
+// The upper-triangle Gram tile deal shared by the fp64 Gram passes — glm.hip (the weighted Gram of the IRLS pass),
+// moments.hip (the diagonal units of the moment pass) and newton.hip (the Hessian and gradient of the Newton pass) —
+// gfx950 / MI355X.
 //
 // The problem they share: a workgroup of 4 waves has staged a batch of 64 rows a_i of NT tiles of 16 columns in LDS
 // (row stride S = 16 NT + 16 doubles, so the four lane groups of a read start 32 banks apart; the columns behind the
@@ -13,6 +14,8 @@
 //   A lane reads its row's NT column values from LDS once per step and uses them for every tile it owns.
 // Tiles: the TU = NT (NT + 1) / 2 upper tiles in the order ta ascending, then tb (tile_a / tile_b); ONES: behind them
 // NT "ones" tiles, A = 1.0 on every lane, whose every result row is the column sum of tile tb (result row 0 is kept).
+// ONES = SCALAR (newton.hip): the same NT tiles with A = the row's scalar sc_{i0+g}, read from wws[64 + row] behind the
+// 64 weights, where the ones tiles have 1.0: every result row is sum_i sc_i a_i[16 tb + m] (result row 0 is kept).
 //
 // Ownership, two rules:
 //   NT >= 3  tile t belongs to wave t mod 4, which runs all 64 rows of the batch for it;
@@ -57,7 +60,10 @@ constexpr int tile_b(int nt, int t) {
     return ta + t;
 }
 
-template <int NT, bool WEIGHTED, bool ONES>
+// the values of ONES: false (0) no such tiles, true (1) the ones tiles, SCALAR the scalar-operand tiles
+constexpr int SCALAR = 2;
+
+template <int NT, bool WEIGHTED, int ONES>
 struct GramTiles {
     static constexpr int S = 16 * NT + 16;              // LDS row stride in doubles
     static constexpr int TU = NT * (NT + 1) / 2;        // upper tiles
@@ -71,15 +77,15 @@ struct GramTiles {
 
     // one step of four rows for the wave's slots s, the tile indices compile-time
     template <int WAVE, int s = 0>
-    static __device__ __forceinline__ void step(d4_t (&acc)[MAXT], double ww, const double (&v)[NT]) {
+    static __device__ __forceinline__ void step(d4_t (&acc)[MAXT], double ww, double sc, const double (&v)[NT]) {
         if constexpr (s < MAXT) {
             constexpr int t = tile(WAVE, s);
             // the tile's indices as constants of their own: left inside the call, their loops run on the device
             constexpr int ta = t < TU ? tile_a(NT, t) : 0, tb = t < TU ? tile_b(NT, t) : t - TU;
             if constexpr (t < TU && WEIGHTED) acc[s] = mf64(ww * v[ta], v[tb], acc[s]);
             else if constexpr (t < TU) acc[s] = mf64(v[ta], v[tb], acc[s]);
-            else if constexpr (t < T) acc[s] = mf64(1.0, v[tb], acc[s]);
-            step<WAVE, s + 1>(acc, ww, v);
+            else if constexpr (t < T) acc[s] = mf64(ONES == SCALAR ? sc : 1.0, v[tb], acc[s]);
+            step<WAVE, s + 1>(acc, ww, sc, v);
         }
     }
 
@@ -91,16 +97,18 @@ struct GramTiles {
 #pragma unroll 2
         for (int r4 = 0; r4 < (SPLIT ? 4 : 16); ++r4) {
             const int row = base + 4 * r4 + g;
-            double ww = 0.0;
+            double ww = 0.0, sc = 0.0;
             if constexpr (WEIGHTED) ww = wws[row];
+            if constexpr (ONES == SCALAR) sc = wws[64 + row];
             double v[NT];
 #pragma unroll
             for (int t = 0; t < NT; ++t) v[t] = rows[row * S + 16 * t + m];
-            step<WAVE>(acc, ww, v);
+            step<WAVE>(acc, ww, sc, v);
         }
     }
 
-    // the batch staged in rows [64 * S] (and wws [64], read when WEIGHTED only) into the wave's accumulators; the
+    // the batch staged in rows [64 * S] (and wws [64], read when WEIGHTED only; SCALAR: wws [128]) into the wave's
+    // accumulators; the
     // caller's barriers stand before it (the batch is staged) and after it (its reads are done)
     static __device__ __forceinline__ void batch(d4_t (&acc)[MAXT], const double* __restrict__ rows,
                                                  const double* __restrict__ wws, int wave, int g, int m) {
@@ -143,6 +151,45 @@ struct GramTiles {
         }
     }
 };
+
+// The row load of the passes that stage whole rows (glm.hip, newton.hip).
+// The row xr [k] as seen by lane sub of its four lanes: v[j] = the columns 8 j + 2 sub and + 1 (zero behind k or
+// when the row is not `ok`; no address is loaded that lies outside the row), and the row's dot with bet (LDS, zero
+// behind k): every lane adds its pairs by fma in ascending j, then the four lanes are added by two xor steps, so
+// all four return the same bits, which depend on the row and k alone.
+template <int NT, bool VEC>
+__device__ __forceinline__ double row_dot(const double* __restrict__ xr, bool ok, int k, int sub,
+                                          const double* __restrict__ bet, d2_t (&v)[2 * NT]) {
+#pragma unroll
+    for (int j = 0; j < 2 * NT; ++j) {
+        const int c = 8 * j + 2 * sub;
+        d2_t t = {0.0, 0.0};
+        if (VEC) {
+            if (ok && c < k) t = *reinterpret_cast<const d2_t*>(xr + c);
+        } else {
+            if (ok && c < k) t[0] = xr[c];
+            if (ok && c + 1 < k) t[1] = xr[c + 1];
+        }
+        v[j] = t;
+    }
+    double dot = 0.0;
+#pragma unroll
+    for (int j = 0; j < 2 * NT; ++j) {
+        const d2_t b = *reinterpret_cast<const d2_t*>(bet + 8 * j + 2 * sub);
+        dot = fma(v[j][0], b[0], dot);
+        dot = fma(v[j][1], b[1], dot);
+    }
+    dot += __shfl_xor(dot, 1, 64);
+    dot += __shfl_xor(dot, 2, 64);
+    return dot;
+}
+
+// beta [k] into bet [128], zero behind k (or everywhere without a beta); every thread of the workgroup calls it
+__device__ __forceinline__ void stage_beta(double* __restrict__ bet, const double* __restrict__ beta, int k) {
+    const int tid = threadIdx.x;
+    if (tid < 128) bet[tid] = (beta != nullptr && tid < k) ? beta[tid] : 0.0;
+    __syncthreads();
+}
 
 namespace {         // a kernel of its own in every file that includes this header
 

@@ -120,12 +120,6 @@ __device__ __forceinline__ int coef_off(const Dims& dm, int l) {
     return o;
 }
 
-__device__ __forceinline__ double group_max(double v) {
-    v = fmax(v, __shfl_xor(v, 16, 64));
-    v = fmax(v, __shfl_xor(v, 32, 64));
-    return v;
-}
-
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);

@@ -53,39 +53,10 @@ constexpr int SM_RED = 1024;        // threads of the sums reduction
 constexpr int SM_WHOLE = 12;        // (tile, chunk) units of 4 KiB of an image that the row pass stages whole
 enum { M_R = 1, M_LOSS = 2 };
 
-__device__ __forceinline__ double group_max(double v) {
-    v = fmax(v, __shfl_xor(v, 16, 64));
-    v = fmax(v, __shfl_xor(v, 32, 64));
-    return v;
-}
-
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
     return v;
-}
-
-// log(1 + sum_c exp(e_c)) of one row from a lane's logits e[t][q] = class 16 t + g + 4 q (classes >= k1 are padding);
-// the four lanes of a row return the same bits
-template <int T>
-__device__ __forceinline__ double row_lse(const d4_t* e, int k1, int g) {
-    double mx = 0.0;        // the pivot's logit
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (16 * t + g + 4 * q < k1) mx = fmax(mx, e[t][q]);
-    }
-    mx = group_max(mx);
-    double se = 0.0;
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (16 * t + g + 4 * q < k1) se += exp(e[t][q] - mx);
-    }
-    se = group_sum(se) + exp(0.0 - mx);
-    return mx + log(se);
 }
 
 // The layout and the tile deal of the gradient pass for T class tiles and MT dim tiles.
