@@ -13,7 +13,7 @@
 //   Gram    after one barrier, the weighted upper tile triangle of gram64_mfma.h (the operand maps, which wave owns
 //           which tile and the order of every addition are described there): at most 9 accumulator tiles per wave.
 //   merge   part [nchunk, 1 + KA KA] holds each chunk's sum ww^2 and the entries of its upper tiles, merged in chunk
-//           order by gram_merge_kernel: the same bits for every grid and run.
+//           order with the mirror map of ordered_sum.h: the same bits for every grid and run.
 //
 // alink_glm_rows_f64: the same row load and dot without the LDS staging, then by mask: pred (mu), eta, the four
 // residuals, z and ww, and per 64-row batch one partial of [deviance, deviance at unlink(cnull + off), pearson^2, w],
@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "gram64_mfma.h"
+#include "ordered_sum.h"
 
 #pragma clang fp contract(off)
 
@@ -166,12 +167,6 @@ __device__ __forceinline__ void f_working(const Fl& f, int mode, double eta, dou
     }
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // pc = the chunk's [sum ww^2 | G [ka, ka]]: acc[s][q] = G[16 ta + g + 4 q][16 tb + m] of slot s's tile
 template <int NT>
 struct GramStore {
@@ -250,7 +245,7 @@ __global__ __launch_bounds__(256, NT == 5 ? 2 : 1) void glm_irls_kernel(
             __syncthreads();
             if (wave == 0) {
                 const double a = wws[lane];
-                sww += wave_sum(a * a);
+                sww += osum::wave_sum_desc(a * a);
             }
             G::batch(acc, rows, wws, wave, g, m);
             __syncthreads();        // the batch's reads are done before the next one is staged
@@ -319,7 +314,7 @@ __global__ __launch_bounds__(256) void glm_rows_kernel(
         }
         if (mask & M_SUMS) {        // one partial per batch: the wave's rows by xor steps, the waves in order
 #pragma unroll
-            for (int q = 0; q < 4; ++q) s[q] = wave_sum(s[q]);
+            for (int q = 0; q < 4; ++q) s[q] = osum::wave_sum_desc(s[q]);
             if (lane == 0) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) ws[wave][q] = s[q];
@@ -375,7 +370,7 @@ int alink_glm_irls_f64(const double* X, const double* y, const double* w, const 
     const unsigned blocks = (unsigned)(grid > 0 && grid < nchunk ? grid : nchunk);
     ALINK_D64_LAUNCH_NT8(glm_irls_kernel, nt, d64::vec_ok(k, X), blocks, st, X, y, w, off, n, k, beta, b0, f, mode,
                          chunk_rows, nchunk, part);
-    d64::gram_merge(1, ka, nchunk, part, out, st);
+    osum::chunk_merge(osum::GramMirror{1, ka}, 1 + (int64_t)ka * ka, nchunk, part, out, st);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

@@ -19,9 +19,8 @@
 //   and a padded slot is never a candidate.  lp_j is parked in R[i, j] by the lane group j & 3, which alone reads
 //   it back: the row's maximum is known by then, each lane group adds exp(lp_j - max) over its own j in ascending
 //   order, the butterfly finishes the sum, lse_i = max + log(sum), and R[i, j] = exp(lp_j - lse_i).
-//   sum_i lse_i: one partial per 64-row batch (rows in lane order, waves in wave order), and a single-workgroup
-//   kernel adds the batch partials by a fixed rule (thread t takes batches t, t + 1024, ... in order, then a fixed
-//   LDS tree).  Neither a row's outputs nor the sum depend on the grid.
+//   sum_i lse_i: one partial per 64-row batch (rows in lane order, waves in wave order), added by the batch sums of
+//   ordered_sum.h, a rule of the batch count alone.  Neither a row's outputs nor the sum depend on the grid.
 // * alink_gmm_em_moments_f64 — the M pass: rs_j = sum_i r_ij, xs_j = sum_i r_ij x0_i, xxs_j = sum_i r_ij x0_i x0_i^T.
 //   Work units are (row chunk, group of 2 or 4 components, tile row ta, block of at most 4 tiles tb >= ta): one wave
 //   per unit (its components share every load of the rows) walks the chunk's rows four at a time (lane group
@@ -29,8 +28,8 @@
 //   of (r . X0)^T X0 on the fp64 MFMA: A = r_i x_i[16 ta + m], B = x_i[16 tb + m].  The units of a chunk are
 //   neighbours in the grid, so the re-reads of its rows meet in L2.
 //   The running sums of A and r in the unit that holds the diagonal tile give xs and rs after the same
-//   butterfly.  Only the upper tile triangle is computed; the merge kernel adds the chunk partials in chunk
-//   order, one lane per output element, reading element (min(a, b), max(a, b)) for both (a, b) and (b, a).  No
+//   butterfly.  Only the upper tile triangle is computed; the chunk partials are merged in chunk order
+//   (ordered_sum.h) with the map EmGather, which reads element (min(a, b), max(a, b)) for both (a, b) and (b, a).  No
 //   float atomics; the chunk length comes from the caller and does not depend on the grid, so the result has the
 //   same bits for every launch and every grid.
 #include <hip/hip_runtime.h>
@@ -38,13 +37,13 @@
 #include <stdint.h>
 
 #include "dense64_mfma.h"
+#include "ordered_sum.h"
 
 namespace {
 
 using namespace d64;
 
 constexpr int EM_M_WAVES = 4;        // waves per workgroup of the M pass, one unit each
-constexpr int EM_RED = 1024;         // threads of the log-likelihood reduction
 
 constexpr int em_group_tiles(int ndch) { return ndch == 1 ? 8 : (ndch == 2 ? 4 : 2); }
 
@@ -160,21 +159,6 @@ __global__ __launch_bounds__(64 * WAVES) void gmm_em_rows_kernel(
             if (tid == 0) part[b] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
         }
     }
-}
-
-// out[0] = the sum of part [nb] by a rule that depends on nb alone
-__global__ __launch_bounds__(EM_RED) void gmm_em_ll_kernel(const double* __restrict__ part, int64_t nb,
-                                                           double* __restrict__ out) {
-    __shared__ double sh[EM_RED];
-    double a = 0.0;
-    for (int64_t i = threadIdx.x; i < nb; i += EM_RED) a += part[i];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = EM_RED / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = sh[0];
 }
 
 // One unit: rows [r0, r1) of the components j0 .. j0 + JB - 1 (those below k), tile row ta, tiles
@@ -319,13 +303,11 @@ __global__ __launch_bounds__(64 * EM_M_WAVES) void gmm_em_moments_kernel(
     }
 }
 
-// out = [rs k | xs k d | xxs k d d]: every element the sum of its chunk partials in chunk order
-__global__ __launch_bounds__(256) void gmm_em_merge_kernel(int k, int d, int64_t nchunk,
-                                                           const double* __restrict__ part,
-                                                           double* __restrict__ out) {
-    const int64_t S = (int64_t)d * d + d + 1;
-    const int64_t total = (int64_t)k * S;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+// the merge's map: element e of out = [rs k | xs k d | xxs k d d] in a chunk's partial [k][d d | d | 1]
+struct EmGather {
+    int k, d;
+    __device__ int64_t operator()(int64_t e) const {
+        const int64_t S = (int64_t)d * d + d + 1;
         int j;
         int64_t off;
         if (e < k) {
@@ -342,11 +324,9 @@ __global__ __launch_bounds__(256) void gmm_em_merge_kernel(int k, int d, int64_t
             const int a = ab / d, b2 = ab - a * d;
             off = a <= b2 ? (int64_t)a * d + b2 : (int64_t)b2 * d + a;
         }
-        double s = part[(int64_t)j * S + off];
-        for (int64_t c = 1; c < nchunk; ++c) s += part[(c * k + j) * S + off];
-        out[e] = s;
+        return (int64_t)j * S + off;
     }
-}
+};
 
 }  // namespace
 
@@ -369,7 +349,7 @@ int alink_gmm_em_rows_f64(const double* X, int64_t n, int d, const double* img, 
     const int64_t nbatch = (n + ROWS - 1) / ROWS;
     ALINK_D64_LAUNCH(gmm_em_rows_kernel, ndch, 1, 2, 3, 4, vec_ok(d, X), row_blocks(n, grid, 2048), st, X, n, d, img,
                      ninit, cst, k, tpc, ngroup, R, arg, part);
-    if (R != nullptr) hipLaunchKernelGGL(gmm_em_ll_kernel, dim3(1), dim3(EM_RED), 0, st, part, nbatch, ll);
+    if (R != nullptr) osum::batch_sums(part, nbatch, 1, ll, st);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -395,9 +375,7 @@ int alink_gmm_em_moments_f64(const double* X, const double* R, int64_t n, int d,
     else if (dt == 3) ALINK_EM_MOMENTS(3);
     else ALINK_EM_MOMENTS(4);
 #undef ALINK_EM_MOMENTS
-    int64_t mblocks = ((int64_t)k * ((int64_t)d * d + d + 1) + 255) / 256;
-    if (mblocks > cap) mblocks = cap;
-    hipLaunchKernelGGL(gmm_em_merge_kernel, dim3((unsigned)mblocks), dim3(256), 0, st, k, d, nchunk, part, out);
+    osum::chunk_merge(EmGather{k, d}, (int64_t)k * ((int64_t)d * d + d + 1), nchunk, part, out, st);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

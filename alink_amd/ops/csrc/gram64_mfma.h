@@ -22,8 +22,10 @@
 //   NT <= 2  (SPLIT) every wave holds all T tiles and runs its own 16 rows of the batch; at the chunk's end the four
 //            waves' partials are added through LDS (`red`) in wave order by wave 0, which stores them.
 // Both rules depend on the width (NT) alone: never on the grid, the chunk length or the row count, so a chunk's
-// partial has the same bits in every launch.  gram_merge_kernel then adds the chunks' partials in chunk order, one
-// lane per output element, and mirrors the lower triangle from the upper: no float atomics anywhere.
+// partial has the same bits in every launch.  The two rules themselves, for any list of T tiles, are WaveDeal, which
+// the gradient pass of softmax_fused.hip deals its own tile list by (mlp_fused.hip keeps the rules written out:
+// profiles/ordered_sum.txt).  The chunks' partials are then merged in chunk order (ordered_sum.h, with the map that
+// mirrors the lower triangle from the upper).
 //
 // The store of a wave's tiles at the chunk's end is the caller's: `finish` takes a type Store with
 //   template <int WAVE> static void store(const d4_t (&acc)[MAXT], Args... args)
@@ -32,7 +34,7 @@
 // the guards of moments.hip to other code and the moment pass measured 0.2 % to 1 % slower at 96 and 128 columns,
 // profiles/gram_shared_triangle.txt.)
 //
-// No contraction: the pragma below covers this header's own code (the weight's multiply, the merge's additions) whatever
+// No contraction: the pragma below covers this header's own code (the weight's multiply, the fold's additions) whatever
 // the including file says later; it stands here, before the first function, because a file-scope pragma holds from
 // where it is written and the including files set theirs only after their includes.
 #pragma once
@@ -63,17 +65,59 @@ constexpr int tile_b(int nt, int t) {
 // the values of ONES: false (0) no such tiles, true (1) the ones tiles, SCALAR the scalar-operand tiles
 constexpr int SCALAR = 2;
 
-template <int NT, bool WEIGHTED, int ONES>
-struct GramTiles {
-    static constexpr int S = 16 * NT + 16;              // LDS row stride in doubles
-    static constexpr int TU = NT * (NT + 1) / 2;        // upper tiles
-    static constexpr int T = TU + (ONES ? NT : 0);      // and the ones tiles behind them
-    static constexpr bool SPLIT = NT <= 2;              // the waves split the rows, not the tiles
+// The deal of a list of T accumulator tiles to the four waves of a workgroup, and the fold at a chunk's end.
+// SPLIT false: tile t belongs to wave t mod 4 (slot t / 4), which runs all 64 rows of a batch for it.  SPLIT true
+// (a short list; the threshold is the caller's): every wave holds all T tiles and runs its own 16 rows.
+template <int T, bool SPLIT_>
+struct WaveDeal {
+    static constexpr bool SPLIT = SPLIT_;               // the waves split the rows, not the tiles
     static constexpr int MAXT = SPLIT ? T : (T + 3) / 4;    // accumulator tiles per wave
     static constexpr int RED = SPLIT ? 4 * T * 256 : 1;     // doubles of the LDS array `red` (32-byte aligned)
 
-    // slot s of wave WAVE
+    // the tile in slot s of wave `wave`
     static constexpr int tile(int wave, int s) { return SPLIT ? s : wave + 4 * s; }
+
+    // the end of a chunk: every thread of the workgroup calls it.  SPLIT: the four waves' partials through red
+    // [RED] in wave order, stored by wave 0 (two barriers, the second so that red may be written again); else every
+    // wave stores its own tiles, Store::store<WAVE>(acc, args...).
+    template <class Store, class... Args>
+    static __device__ __forceinline__ void finish(d4_t (&acc)[MAXT], double* __restrict__ red, int wave, int lane,
+                                                  Args... args) {
+        if constexpr (SPLIT) {
+#pragma unroll
+            for (int s = 0; s < MAXT; ++s) *reinterpret_cast<d4_t*>(red + ((wave * T + s) * 64 + lane) * 4) = acc[s];
+            __syncthreads();
+            if (wave == 0) {
+#pragma unroll
+                for (int s = 0; s < MAXT; ++s) {
+                    d4_t a = *reinterpret_cast<const d4_t*>(red + (s * 64 + lane) * 4);
+                    for (int ws = 1; ws < 4; ++ws)
+                        a += *reinterpret_cast<const d4_t*>(red + ((ws * T + s) * 64 + lane) * 4);
+                    acc[s] = a;
+                }
+                Store::template store<0>(acc, args...);
+            }
+            __syncthreads();
+        } else {
+            switch (wave) {
+                case 0: Store::template store<0>(acc, args...); break;
+                case 1: Store::template store<1>(acc, args...); break;
+                case 2: Store::template store<2>(acc, args...); break;
+                default: Store::template store<3>(acc, args...); break;
+            }
+        }
+    }
+};
+
+template <int NT, bool WEIGHTED, int ONES>
+struct GramTiles : WaveDeal<NT * (NT + 1) / 2 + (ONES ? NT : 0), (NT <= 2)> {
+    using Deal = WaveDeal<NT * (NT + 1) / 2 + (ONES ? NT : 0), (NT <= 2)>;
+    using Deal::MAXT;
+    using Deal::SPLIT;
+    using Deal::tile;
+    static constexpr int S = 16 * NT + 16;              // LDS row stride in doubles
+    static constexpr int TU = NT * (NT + 1) / 2;        // upper tiles
+    static constexpr int T = TU + (ONES ? NT : 0);      // and the ones tiles behind them
 
     // one step of four rows for the wave's slots s, the tile indices compile-time
     template <int WAVE, int s = 0>
@@ -119,37 +163,6 @@ struct GramTiles {
             default: batch_of<3>(acc, rows, wws, wave, g, m); break;
         }
     }
-
-    // the end of a chunk: every thread of the workgroup calls it.  SPLIT: the four waves' partials through red
-    // [RED] in wave order, stored by wave 0 (two barriers, and a third so that red may be written again); else every
-    // wave stores its own tiles, Store::store<WAVE>(acc, args...).
-    template <class Store, class... Args>
-    static __device__ __forceinline__ void finish(d4_t (&acc)[MAXT], double* __restrict__ red, int wave, int lane,
-                                                  Args... args) {
-        if constexpr (SPLIT) {
-#pragma unroll
-            for (int s = 0; s < MAXT; ++s) *reinterpret_cast<d4_t*>(red + ((wave * T + s) * 64 + lane) * 4) = acc[s];
-            __syncthreads();
-            if (wave == 0) {
-#pragma unroll
-                for (int s = 0; s < MAXT; ++s) {
-                    d4_t a = *reinterpret_cast<const d4_t*>(red + (s * 64 + lane) * 4);
-                    for (int ws = 1; ws < 4; ++ws)
-                        a += *reinterpret_cast<const d4_t*>(red + ((ws * T + s) * 64 + lane) * 4);
-                    acc[s] = a;
-                }
-                Store::template store<0>(acc, args...);
-            }
-            __syncthreads();
-        } else {
-            switch (wave) {
-                case 0: Store::template store<0>(acc, args...); break;
-                case 1: Store::template store<1>(acc, args...); break;
-                case 2: Store::template store<2>(acc, args...); break;
-                default: Store::template store<3>(acc, args...); break;
-            }
-        }
-    }
 };
 
 // The row load of the passes that stage whole rows (glm.hip, newton.hip).
@@ -190,41 +203,5 @@ __device__ __forceinline__ void stage_beta(double* __restrict__ bet, const doubl
     if (tid < 128) bet[tid] = (beta != nullptr && tid < k) ? beta[tid] : 0.0;
     __syncthreads();
 }
-
-namespace {         // a kernel of its own in every file that includes this header
-
-// part [nchunk, head + dim dim] -> out [head + dim dim]: every element the sum of its chunk partials in chunk order,
-// the lower triangle of the dim x dim matrix behind the `head` leading entries read from the upper
-__global__ __launch_bounds__(256) void gram_merge_kernel(int head, int dim, int64_t nchunk,
-                                                         const double* __restrict__ part, double* __restrict__ out) {
-    const int64_t P = head + (int64_t)dim * dim;
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= P) return;
-    int64_t src = e;
-    if (e >= head) {
-        const int a = (int)((e - head) / dim), b = (int)((e - head) - (int64_t)a * dim);
-        src = head + (a <= b ? (int64_t)a * dim + b : (int64_t)b * dim + a);
-    }
-    double s = part[src];
-    int64_t c = 1;
-    for (; c + 8 <= nchunk; c += 8) {       // eight loads in flight, added in chunk order
-        double t[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) t[u] = part[(c + u) * P + src];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += t[u];
-    }
-    for (; c < nchunk; ++c) s += part[c * P + src];
-    out[e] = s;
-}
-
-// host side: its launch on stream st
-inline void gram_merge(int head, int dim, int64_t nchunk, const double* part, double* out, hipStream_t st) {
-    const int64_t P = head + (int64_t)dim * dim;
-    hipLaunchKernelGGL(gram_merge_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, head, dim, nchunk, part,
-                       out);
-}
-
-}  // namespace
 
 }  // namespace d64

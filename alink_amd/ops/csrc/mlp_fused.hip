@@ -37,12 +37,13 @@
 //             dW_l[16 ta + g + 4 q][16 tb + mm]); the tiles of all layers form one list (layer, ta, tb ascending) and
 //             tile t belongs to wave t mod 4, accumulator t / 4 (at most 10 per wave), kept in registers for the whole
 //             chunk; a list shorter than 4 tiles is held by every wave for its own 16 rows and the waves are added
-//             through LDS in wave order at the chunk's end.  db_l: thread (wave, lane) adds column `lane` of D_{l+1}
-//             over the wave's 16 rows in row order, batch after batch; the four waves are added in wave order at the
-//             chunk's end.  D_l = (D_{l+1} W_l^T) * S_l (1 - S_l) on MFMA against the bwd image, each wave for its own
-//             rows, and written over S_l once a second barrier says every wave's Gram reads of S_l are done.
-//   merge     part [nchunk, 1 + nw]; one lane per element adds the chunks in chunk order.  No float atomics: the same
-//             bits for every grid and run.
+//             through LDS in wave order at the chunk's end (the rules of WaveDeal in gram64_mfma.h, written out here:
+//             its finish, with the store dispatched per wave, measured 46 % slower in this kernel,
+//             profiles/ordered_sum.txt).  db_l: thread (wave, lane) adds column `lane` of D_{l+1} over the wave's 16
+//             rows in row order, batch after batch; the four waves are added in wave order at the chunk's end.
+//             D_l = (D_{l+1} W_l^T) * S_l (1 - S_l) on MFMA against the bwd image, each wave for its own rows, and
+//             written over S_l once a second barrier says every wave's Gram reads of S_l are done.
+//   merge     part [nchunk, 1 + nw], merged in chunk order (ordered_sum.h): the same bits for every grid and run.
 // LDS plan of the gradient pass (bytes; rows 16 T doubles apart, columns xor-ed with 16 on odd rows when T is even, so
 // that rows of either parity start 32 banks apart):
 //   xs  X batch         64 x 16 TI x 8   =  8 / 16 / 32 / 64 KiB
@@ -59,7 +60,7 @@
 // tiles of 16 for groups of 8 / T1 sets at once (T1 = out tiles of layer 0; 8 accumulator tiles), so X is read from
 // memory once and again from the caches for a further group; the group's first-layer outputs go to LDS (64 KiB), and
 // the rest of the network runs set by set from there.  Outputs by mask: 1 sums [S] = sum w (lse - z[y]) (one partial
-// per 64-row batch and set, part [S, nb], added per set by one workgroup by a rule of nb alone: independent of the
+// per 64-row batch and set, part [S, nb], added per set by the batch sums of ordered_sum.h: independent of the
 // grid); for S = 1: 2 row_loss [n] = min(lse - z[y], -log(1e-300)) (the clamp of -log(max(P[y], 1e-300))), 4 P [n, C]
 // = exp(z - mx) / se, 8 label [n] (int32) = the first maximum of the logits (own accumulators in ascending class
 // order first, the four lane groups last, the lower class on equal bits; never a padded slot).
@@ -68,6 +69,7 @@
 #include <stdint.h>
 
 #include "dense64_mfma.h"
+#include "ordered_sum.h"
 
 #pragma clang fp contract(off)
 
@@ -76,7 +78,6 @@ namespace {
 using namespace d64;
 
 constexpr int ML_MAX_IN = 128, ML_MAX_HIDDEN = 64, ML_MAX_CLASSES = 64, ML_ROWS_MAX_IN = 1024, ML_MAX_STEPS = 8;
-constexpr int ML_RED = 1024;                // threads of the sums reduction
 constexpr int ML_LDS = 160 * 1024 - 512;    // what a workgroup may take
 constexpr int ML_MAX_TILES = 40;            // Gram tiles of all layers: more spill to scratch
 enum { M_LOSS = 1, M_ROW_LOSS = 2, M_P = 4, M_LABEL = 8 };
@@ -118,12 +119,6 @@ __device__ __forceinline__ int coef_off(const Dims& dm, int l) {
     int o = 0;
     for (int i = 0; i < l; ++i) o += dm.d[i] * dm.d[i + 1] + dm.d[i + 1];
     return o;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // LDS writes of this wave's lanes become visible to its other lanes: the wave's DS operations complete in order, so
@@ -402,7 +397,7 @@ __global__ __launch_bounds__(256) void mlp_grad_kernel(
             __syncthreads();        // the batch's reads are done before the next one is staged
         }
         double* __restrict__ pc = part + c * P;
-        lsum = wave_sum(lsum);      // the lanes with g > 0 add zeros
+        lsum = osum::wave_sum_asc(lsum);    // the lanes with g > 0 add zeros
         if (lane == 0) wl[wave] = lsum;
 #pragma unroll
         for (int l = 0; l < NL; ++l) dbr[l][wave][lane] = db[l];
@@ -436,24 +431,6 @@ __global__ __launch_bounds__(256) void mlp_grad_kernel(
         }
         __syncthreads();            // wl, dbr and red may be written again
     }
-}
-
-// part [nchunk, P] -> out [P]: every element the sum of its chunk partials in chunk order
-__global__ __launch_bounds__(256) void mlp_merge_kernel(int64_t P, int64_t nchunk, const double* __restrict__ part,
-                                                        double* __restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= P) return;
-    double s = part[e];
-    int64_t c = 1;
-    for (; c + 8 <= nchunk; c += 8) {       // eight loads in flight, added in chunk order
-        double t[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) t[u] = part[(c + u) * P + e];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += t[u];
-    }
-    for (; c < nchunk; ++c) s += part[c * P + e];
-    out[e] = s;
 }
 
 template <int NL, int TH, int TO, bool VEC>
@@ -549,7 +526,7 @@ __global__ __launch_bounds__(256) void mlp_rows_kernel(
                 }
                 zy = group_sum(zy);
                 if (mask & M_LOSS) {
-                    const double v = wave_sum(g == 0 ? (lse - zy) * wi : 0.0);
+                    const double v = osum::wave_sum_asc(g == 0 ? (lse - zy) * wi : 0.0);
                     if (lane == 0) ws[s0 + j][wave] = v;
                 }
                 if ((mask & M_ROW_LOSS) && ok && g == 0) row_loss[row] = fmin(lse - zy, -log(1e-300));
@@ -574,22 +551,6 @@ __global__ __launch_bounds__(256) void mlp_rows_kernel(
             __syncthreads();        // ws may be written again
         }
     }
-}
-
-// out [gridDim] = per set the sum of its nb batch partials, by a rule of nb alone
-__global__ __launch_bounds__(ML_RED) void mlp_sums_kernel(const double* __restrict__ part, int64_t nb,
-                                                          double* __restrict__ out) {
-    __shared__ double sh[ML_RED];
-    const double* __restrict__ p = part + (int64_t)blockIdx.x * nb;
-    double a = 0.0;
-    for (int64_t i = threadIdx.x; i < nb; i += ML_RED) a += p[i];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = ML_RED / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
 }
 
 template <int NL, int TI, int TH, class... A>
@@ -698,7 +659,7 @@ int alink_mlp_fused_grad_f64(const double* X, const double* y, const double* w, 
     else if (nl == 2) ok = grad_ti<2>(ti, th, to, blocks, st, X, y, w, n, dm, pack, vec, chunk_rows, nchunk, P, part);
     else ok = grad_ti<3>(ti, th, to, blocks, st, X, y, w, n, dm, pack, vec, chunk_rows, nchunk, P, part);
     if (!ok) return 1;
-    hipLaunchKernelGGL(mlp_merge_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, P, nchunk, part, out);
+    osum::chunk_merge(osum::Identity{}, P, nchunk, part, out, st);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -726,7 +687,7 @@ int alink_mlp_fused_rows_f64(const double* X, const double* y, const double* w, 
     if (nl == 1) rows_th<1>(th, to, vec, blocks, st, X, y, w, n, dm, pack, nti, nsets, mask, part, nb, row_loss, P, label);
     else if (nl == 2) rows_th<2>(th, to, vec, blocks, st, X, y, w, n, dm, pack, nti, nsets, mask, part, nb, row_loss, P, label);
     else rows_th<3>(th, to, vec, blocks, st, X, y, w, n, dm, pack, nti, nsets, mask, part, nb, row_loss, P, label);
-    if (mask & M_LOSS) hipLaunchKernelGGL(mlp_sums_kernel, dim3((unsigned)nsets), dim3(ML_RED), 0, st, part, nb, out);
+    if (mask & M_LOSS) osum::batch_sums(part, nb, nsets, out, st);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

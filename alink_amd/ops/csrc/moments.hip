@@ -17,9 +17,8 @@
 //             and all nb tile columns, 16 tiles at most.
 //           Both rules depend on (d, A, B) alone, and t comes out of the matrix instruction: nothing depends on
 //           the grid.
-//   merge   part [nchunk, d + d d] holds each chunk's t and the entries of its upper tiles, merged in chunk order by
-//           gram_merge_kernel, which mirrors the triangle, so C is exactly symmetric: the same bits for every grid
-//           and run.
+//   merge   part [nchunk, d + d d] holds each chunk's t and the entries of its upper tiles, merged in chunk order
+//           with the mirror map of ordered_sum.h, so C is exactly symmetric: the same bits for every grid and run.
 // The diagonal units of the full blocks, the diagonal unit of a last block of fewer tiles and the off-diagonal units
 // are three launches (each kernel has its own tile count at compile time); they write disjoint parts of `part`.
 //
@@ -46,7 +45,7 @@
 //           One rule for every width: tile t of the unit's list belongs to wave t mod 4, which runs all 64 rows of a
 //           batch for it (at NT = 1 the four waves hold N, P, S and Q).  It depends on (d, A, B) alone.  No
 //           instantiation spills, so no deal was narrowed.
-//   merge   part [nchunk, 4 d d], merged in chunk order by pairwise_merge_kernel, which mirrors the lower triangles
+//   merge   part [nchunk, 4 d d], merged in chunk order with the map PairwiseMirror, which mirrors the lower triangles
 //           of N and P only: they are exactly symmetric, S and Q stay as computed; no float atomics, the same bits
 //           for every grid, run and alignment.
 // The diagonal units of the full blocks, of a ragged last block, the off-diagonal units between full blocks and those
@@ -57,6 +56,7 @@
 #include <stdint.h>
 
 #include "gram64_mfma.h"
+#include "ordered_sum.h"
 
 #pragma clang fp contract(off)
 
@@ -548,28 +548,17 @@ __global__ __launch_bounds__(256) void pairwise_off_kernel(const double* __restr
     pairwise_units<4, NB, true, VEC>(X, n, d, shift, blk0, npair, last, chunk_rows, nchunk, part);
 }
 
-// part [nchunk, 4 d d] -> out [4, d, d]: every element the sum of its chunk partials in chunk order; the lower
-// triangles of N (plane 0) and P (plane 3) are read from the upper, S and Q are left as computed
-__global__ __launch_bounds__(256) void pairwise_merge_kernel(int d, int64_t nchunk, const double* __restrict__ part,
-                                                             double* __restrict__ out) {
-    const int64_t dd = (int64_t)d * d, P = 4 * dd;
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= P) return;
-    const int f = (int)(e / dd);
-    const int a = (int)((e - f * dd) / d), b = (int)((e - f * dd) - (int64_t)a * d);
-    const int64_t src = ((f == 0 || f == 3) && a > b) ? f * dd + (int64_t)b * d + a : e;
-    double s = part[src];
-    int64_t c = 1;
-    for (; c + 8 <= nchunk; c += 8) {       // eight loads in flight, added in chunk order
-        double t[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) t[u] = part[(c + u) * P + src];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += t[u];
+// the merge's map for [4, d, d]: the lower triangles of N (plane 0) and P (plane 3) are read from the upper, S and Q
+// are left as computed
+struct PairwiseMirror {
+    int d;
+    __device__ int64_t operator()(int64_t e) const {
+        const int64_t dd = (int64_t)d * d;
+        const int f = (int)(e / dd);
+        const int a = (int)((e - f * dd) / d), b = (int)((e - f * dd) - (int64_t)a * d);
+        return ((f == 0 || f == 3) && a > b) ? f * dd + (int64_t)b * d + a : e;
     }
-    for (; c < nchunk; ++c) s += part[c * P + src];
-    out[e] = s;
-}
+};
 
 }  // namespace
 
@@ -603,7 +592,7 @@ int alink_moments_f64(const double* X, int64_t n, int d, const double* shift, in
             hipLaunchKernelGGL(moments_off_kernel<false>, dim3(ob), dim3(256), 0, st, X, n, d, shift, nblk, crows,
                                nchunk, part);
     }
-    gram_merge(d, d, nchunk, part, out, st);
+    osum::chunk_merge(osum::GramMirror{d, d}, d + (int64_t)d * d, nchunk, part, out, st);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -634,8 +623,7 @@ int alink_pairwise_moments_f64(const double* X, int64_t n, int d, const double* 
     if (nfull > 0 && ntl > 0)
         ALINK_D64_LAUNCH(pairwise_off_kernel, ntl, 1, 2, 3, 4, vec, blocks(nchunk * nfull), st, X, n, d, shift, nfull,
                          nfull, nfull, crows, nchunk, part);
-    const int64_t P = 4 * (int64_t)d * d;
-    hipLaunchKernelGGL(pairwise_merge_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, d, nchunk, part, out);
+    osum::chunk_merge(PairwiseMirror{d}, 4 * (int64_t)d * d, nchunk, part, out, st);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

@@ -23,8 +23,8 @@
 //           wave, in registers for the whole chunk.  Wave 0 adds the four sum terms, the rows by xor steps, the batches
 //           in order.
 //   merge   part [nchunk, 4 + k + k k] holds each chunk's sums, g and the entries of its upper tiles, merged in chunk
-//           order by gram_merge_kernel, which also mirrors the triangle: no float atomics, the same bits for every
-//           grid and run.  A loss with l'' = 0 (hinge, perceptron, SVR) gives ww = 0 and H = 0 exactly.
+//           order with the mirror map of ordered_sum.h: no float atomics, the same bits for every grid and run.  A
+//           loss with l'' = 0 (hinge, perceptron, SVR) gives ww = 0 and H = 0 exactly.
 //
 // All arithmetic is fp64 and follows the torch formulas operation for operation (no contraction: the only fused
 // operations are the explicit fma of the dot and the matrix instruction).
@@ -33,6 +33,7 @@
 #include <stdint.h>
 
 #include "gram64_mfma.h"
+#include "ordered_sum.h"
 
 #pragma clang fp contract(off)
 
@@ -149,12 +150,6 @@ __device__ __forceinline__ RowTerms row_terms(int code, double p, double eta, do
     return r;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // pc = the chunk's [sums (4) | g [k] | H [k, k]]: acc[s][q] = H[16 ta + g + 4 q][16 tb + m] of an upper tile, and
 // result row 0 (g = 0, q = 0) of scalar tile tb = g[16 tb + m]
 template <int NT>
@@ -227,7 +222,7 @@ __global__ __launch_bounds__(256) void newton_unary_kernel(
             __syncthreads();
             if (wave == 0) {
 #pragma unroll
-                for (int q = 0; q < NW_SUMS; ++q) sums[q] += wave_sum(terms[q][lane]);
+                for (int q = 0; q < NW_SUMS; ++q) sums[q] += osum::wave_sum_desc(terms[q][lane]);
             }
             G::batch(acc, rows, wws, wave, g, m);
             __syncthreads();        // the batch's reads are done before the next one is staged
@@ -259,9 +254,9 @@ __global__ __launch_bounds__(256) void newton_unary_kernel(
 //           the scalar sc = w (phi_s - [y = s]) (0 otherwise) beside the rows; then each pair runs the tile deal of
 //           gram64_mfma.h into accumulators of its own.  The scalar-operand tiles of a diagonal pair give G[s]; the
 //           unit that holds pair (0, 0) adds the two sums.  Every element comes from exactly one unit.
-//   merge   newton_softmax_merge_kernel adds the chunk partials in chunk order, one lane per element of the output,
-//           which reads block (min(s, t), max(s, t)) at (min(a, b), max(a, b)): the transposed blocks and the mirror
-//           inside a block in one rule, so H is exactly symmetric.  No [n, k1] block is written to memory.
+//   merge   the chunk partials are merged in chunk order (ordered_sum.h) with the map SoftmaxMirror: an element of
+//           the output reads block (min(s, t), max(s, t)) at (min(a, b), max(a, b)): the transposed blocks and the
+//           mirror inside a block in one rule, so H is exactly symmetric.  No [n, k1] block is written to memory.
 // The logits of a unit's batch are recomputed by every pair group: T MT of the unit's T MT + PG (TU + NT) matrix
 // instructions per 16 rows and wave (profiles/newton.txt has the share at the measured shapes).
 
@@ -414,8 +409,8 @@ __global__ __launch_bounds__(256) void newton_softmax_kernel(
                 wws[j][64 + lane] = sc;
             }
             if (wave == 0 && grp == 0) {
-                sums[0] += wave_sum(wl[lane]);
-                sums[1] += wave_sum(ll[lane]);
+                sums[0] += osum::wave_sum_desc(wl[lane]);
+                sums[1] += osum::wave_sum_desc(ll[lane]);
             }
             __syncthreads();
 #pragma unroll
@@ -435,25 +430,19 @@ __global__ __launch_bounds__(256) void newton_softmax_kernel(
     }
 }
 
-// part [nchunk, 2 + D + D D] -> out: every element the sum of its chunk partials in chunk order; element
-// [(s, a), (t, b)] of H reads block (min(s, t), max(s, t)) at (min(a, b), max(a, b))
-__global__ __launch_bounds__(256) void newton_softmax_merge_kernel(int m, int64_t D, int64_t nchunk,
-                                                                   const double* __restrict__ part,
-                                                                   double* __restrict__ out) {
-    const int64_t P = 2 + D + D * D;
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= P) return;
-    int64_t src = e;
-    if (e >= 2 + D) {
+// the merge's map for [sums (2) | G [D] | H [D, D]]: element [(s, a), (t, b)] of H reads block (min(s, t), max(s, t))
+// at (min(a, b), max(a, b))
+struct SoftmaxMirror {
+    int m;
+    int64_t D;
+    __device__ int64_t operator()(int64_t e) const {
+        if (e < 2 + D) return e;
         const int64_t A = (e - 2 - D) / D, B = (e - 2 - D) - A * D;
         const int s = (int)(A / m), a = (int)(A - (int64_t)s * m), t = (int)(B / m), b = (int)(B - (int64_t)t * m);
         const int s0 = s < t ? s : t, t0 = s < t ? t : s, a0 = a < b ? a : b, b0 = a < b ? b : a;
-        src = 2 + D + ((int64_t)s0 * m + a0) * D + (int64_t)t0 * m + b0;
+        return 2 + D + ((int64_t)s0 * m + a0) * D + (int64_t)t0 * m + b0;
     }
-    double v = part[src];
-    for (int64_t c = 1; c < nchunk; ++c) v += part[c * P + src];
-    out[e] = v;
-}
+};
 
 template <int T, bool VEC, class... Args>
 void launch_softmax(int nt, unsigned blocks, hipStream_t st, Args... a) {
@@ -513,7 +502,7 @@ int alink_newton_unary_f64(const double* X, const double* y, const double* w, co
     const unsigned blocks = (unsigned)(grid > 0 && grid < nchunk ? grid : nchunk);
     ALINK_D64_LAUNCH_NT8(newton_unary_kernel, nt, d64::vec_ok(k, X), blocks, st, X, y, w, coef, n, k, code, param,
                          chunk_rows, nchunk, part);
-    d64::gram_merge(NW_SUMS + k, k, nchunk, part, out, st);
+    osum::chunk_merge(osum::GramMirror{NW_SUMS + k, k}, NW_SUMS + k + (int64_t)k * k, nchunk, part, out, st);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -537,8 +526,7 @@ int alink_newton_softmax_f64(const double* X, const double* y, const double* w, 
         launch_softmax_t<true>(t, nt, blocks, st, X, y, w, n, m, k1, img, chunk_rows, nchunk, ngroup, part);
     else
         launch_softmax_t<false>(t, nt, blocks, st, X, y, w, n, m, k1, img, chunk_rows, nchunk, ngroup, part);
-    hipLaunchKernelGGL(newton_softmax_merge_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, m, D, nchunk,
-                       part, out);
+    osum::chunk_merge(SoftmaxMirror{m, D}, P, nchunk, part, out, st);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

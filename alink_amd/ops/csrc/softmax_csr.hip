@@ -18,7 +18,7 @@
 //           the row is read once.
 //   sums    a wave's work item is a block of SMC_RB consecutive rows, walked in row order; lane s keeps the running sum
 //           of step s (lane 0 the plain loss sum), so a block gives one partial per step, part [nsteps, nb].
-//           smc_sums_kernel adds a step's partials by a rule of nb alone.  Nothing depends on the grid.
+//           The batch sums of ordered_sum.h add a step's partials by a rule of nb alone.  Nothing depends on the grid.
 //   outputs by mask: R [n, k1]; the loss sum(s); the per-row loss without the weight.
 //
 // alink_softmax_csr_grad: Gt [m, k1], Gt[j, c] = sum over the entries (i, j, v) of v R[i, c], through the CSC view and
@@ -33,6 +33,7 @@
 #include <math.h>
 
 #include "csr_rows.h"
+#include "ordered_sum.h"
 
 #pragma clang fp contract(off)
 
@@ -42,7 +43,6 @@ using csr::WAVES;
 
 constexpr int SMC_KMAX = 64, SMC_MAX_STEPS = 64;
 constexpr int SMC_RB = 16;          // rows of one loss partial (a wave's work item)
-constexpr int SMC_RED = 1024;       // threads of the sums reduction
 constexpr int SMC_GU = 4;           // steps of the gather whose loads are issued together
 constexpr int SMC_MU = 16;          // chunk partials the merge loads together
 enum { M_R = 1, M_LOSS = 2, M_ROWLOSS = 4 };
@@ -53,16 +53,10 @@ __device__ __forceinline__ double wave_max(double v) {
     return v;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // log(1 + sum_{c < k1} exp(e_c)) of the row whose class `lane` has the logit e; the same on every lane
 __device__ __forceinline__ double row_lse(double e, bool cls) {
     const double mx = wave_max(cls ? fmax(0.0, e) : 0.0);
-    const double se = wave_sum(cls ? exp(e - mx) : 0.0) + exp(0.0 - mx);
+    const double se = osum::wave_sum_asc(cls ? exp(e - mx) : 0.0) + exp(0.0 - mx);
     return mx + log(se);
 }
 
@@ -112,31 +106,6 @@ __global__ __launch_bounds__(64 * WAVES) void smc_rows_kernel(
         }
         if ((SEARCH || (mask & M_LOSS)) && lane < nsteps) part[(int64_t)lane * nb + b] = lsum;
     }
-}
-
-// out [gridDim] = per step the sum of its nb block partials: a thread adds its partials in ascending order (eight
-// loads in flight), then the fixed tree over the threads; a rule of nb alone
-__global__ __launch_bounds__(SMC_RED) void smc_sums_kernel(const double* __restrict__ part, int64_t nb,
-                                                           double* __restrict__ out) {
-    __shared__ double sh[SMC_RED];
-    const double* __restrict__ p = part + (int64_t)blockIdx.x * nb;
-    double a = 0.0;
-    int64_t i = threadIdx.x;
-    for (; i + 7 * SMC_RED < nb; i += 8 * SMC_RED) {
-        double t[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) t[u] = p[i + u * SMC_RED];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) a += t[u];
-    }
-    for (; i < nb; i += SMC_RED) a += p[i];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = SMC_RED / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
 }
 
 // One wave per work item: entries [wstart, wstart + wlen) of the CSC arrays, all of column wcol.  P: k1 rounded up to
@@ -249,7 +218,7 @@ int alink_softmax_csr_rows(const int64_t* crow, const void* col, int idx64, cons
         ALINK_CSR_LAUNCH_IDX((smc_rows_kernel<false, int64_t>), (smc_rows_kernel<false, int32_t>), idx64, blocks, st,
                              crow, col, val, n, m, y, w, k1, T, beta, nsteps, mask, R, rloss, part, nb);
     if (search || (mask & M_LOSS))
-        hipLaunchKernelGGL(smc_sums_kernel, dim3((unsigned)nsteps), dim3(SMC_RED), 0, st, part, nb, out);
+        osum::batch_sums(part, nb, nsteps, out, st);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

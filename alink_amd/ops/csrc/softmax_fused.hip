@@ -19,11 +19,10 @@
 //           rows, so that rows of either parity start 32 banks apart in every case.
 //   Gram    after one barrier G += r^T x on v_mfma_f64_16x16x4_f64, four rows per instruction: A[mm][g] =
 //           r[i0 + g][16 tc + mm], B[g][mm] = x[i0 + g][16 td + mm], result slot q = G[16 tc + g + 4 q][16 td + mm].
-//           Tile t = tc MT + td belongs to wave t mod 4, which runs all 64 rows for it (at most 8 accumulator
-//           tiles); with fewer than 4 tiles every wave holds them all and runs its own 16 rows, and the four waves'
-//           partials are added through LDS in wave order at the chunk's end.  Both rules depend on (k1, m) alone.
-//   merge   part [nchunk, 1 + k1 m] holds each chunk's loss sum and G; one lane per element adds them in chunk order.
-//           No float atomics: the same bits for every grid and run.
+//           The tiles t = tc MT + td are dealt to the waves by WaveDeal of gram64_mfma.h (at most 8 accumulator
+//           tiles per wave), the split rule for fewer than 4 tiles: a rule of (k1, m) alone.
+//   merge   part [nchunk, 1 + k1 m] holds each chunk's loss sum and G, merged in chunk order (ordered_sum.h): the
+//           same bits for every grid and run.
 //
 // alink_softmax_fused_rows_f64 (1 <= m <= 1024): the chunk-walking tile loop of dense64_mfma.h (load_chunk, stage,
 // mfma_group, the lane-ordered image of one block of NT tiles).  Plain: the table is W (TW = 1, 2 or 4 class tiles);
@@ -31,8 +30,8 @@
 // class tile t of W and of D land in the same lane slots (accumulators t and TW + t); a row evaluates
 // w (lse(e_s) - e_s[y]) for e_s = ec - s (beta ed), s < nsteps <= 64, in registers.  An image of at most 48 KiB is
 // staged whole, once per workgroup; a larger one chunk by chunk.  Sums: one partial per 64-row batch and step (the
-// wave's rows by xor steps, the waves in wave order), part [nsteps, nb], added per step by one workgroup by a rule of
-// nb alone: independent of the grid.
+// wave's rows by xor steps, the waves in wave order), part [nsteps, nb], added per step by the batch sums of
+// ordered_sum.h: independent of the grid.
 //
 // The formulas follow ops/softmax.softmax_grad_torch / softmax_search_torch operation for operation (no contraction:
 // the only fused operation is the matrix instruction).
@@ -40,7 +39,8 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "dense64_mfma.h"
+#include "gram64_mfma.h"
+#include "ordered_sum.h"
 
 #pragma clang fp contract(off)
 
@@ -49,28 +49,21 @@ namespace {
 using namespace d64;
 
 constexpr int SM_KMAX = 64, SM_GRAD_MAX_M = 128, SM_MAX_M = 1024, SM_MAX_STEPS = 64;
-constexpr int SM_RED = 1024;        // threads of the sums reduction
 constexpr int SM_WHOLE = 12;        // (tile, chunk) units of 4 KiB of an image that the row pass stages whole
 enum { M_R = 1, M_LOSS = 2 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // The layout and the tile deal of the gradient pass for T class tiles and MT dim tiles.
 template <int T, int MT>
-struct GradTiles {
+struct GradTiles : WaveDeal<T * MT, (T * MT < 4)> {
+    using Deal = WaveDeal<T * MT, (T * MT < 4)>;
+    using Deal::MAXT;
+    using Deal::SPLIT;
+    using Deal::tile;
     static constexpr int NDCH = (MT + 1) / 2;
     static constexpr int SX = 16 * MT, SR = 16 * T;             // LDS row strides in doubles
     static constexpr bool XSW = MT % 2 == 0, RSW = T % 2 == 0;  // xor 16 into the columns of odd rows
     static constexpr int NTILES = T * MT;
-    static constexpr bool SPLIT = NTILES < 4;                   // the waves split the rows, not the tiles
-    static constexpr int MAXT = SPLIT ? NTILES : (NTILES + 3) / 4;
-    static constexpr int RED = SPLIT ? 4 * NTILES * 256 : 4;
     static constexpr bool W_LDS = T * NDCH < 16;
-    static constexpr int tile(int wave, int s) { return SPLIT ? s : wave + 4 * s; }
 
     template <int WAVE, int s = 0>
     static __device__ __forceinline__ void step(d4_t (&acc)[MAXT], const double (&a)[T], const double (&b)[MT]) {
@@ -108,7 +101,7 @@ struct GradTiles {
         }
     }
 
-    // pc = the chunk's [loss | G [k1, m]]: slot s, q of a lane is G[16 tc + g + 4 q][16 td + mm]
+    // pc = the chunk's [loss | G [k1, m]]: slot s, q of a lane is G[16 tc + g + 4 q][16 td + mm]; the Store of finish
     template <int WAVE, int s = 0>
     static __device__ __forceinline__ void store(const d4_t (&acc)[MAXT], double* __restrict__ pc, int k1, int m,
                                                  int g, int mm) {
@@ -123,35 +116,6 @@ struct GradTiles {
                 }
             }
             store<WAVE, s + 1>(acc, pc, k1, m, g, mm);
-        }
-    }
-
-    // the end of a chunk; every thread of the workgroup calls it
-    static __device__ __forceinline__ void finish(d4_t (&acc)[MAXT], double* __restrict__ red, int wave, int lane,
-                                                  double* __restrict__ pc, int k1, int m, int g, int mm) {
-        if constexpr (SPLIT) {
-#pragma unroll
-            for (int s = 0; s < MAXT; ++s)
-                *reinterpret_cast<d4_t*>(red + ((wave * NTILES + s) * 64 + lane) * 4) = acc[s];
-            __syncthreads();
-            if (wave == 0) {
-#pragma unroll
-                for (int s = 0; s < MAXT; ++s) {
-                    d4_t a = *reinterpret_cast<const d4_t*>(red + (s * 64 + lane) * 4);
-                    for (int ws = 1; ws < 4; ++ws)
-                        a += *reinterpret_cast<const d4_t*>(red + ((ws * NTILES + s) * 64 + lane) * 4);
-                    acc[s] = a;
-                }
-                store<0>(acc, pc, k1, m, g, mm);
-            }
-            __syncthreads();
-        } else {
-            switch (wave) {
-                case 0: store<0>(acc, pc, k1, m, g, mm); break;
-                case 1: store<1>(acc, pc, k1, m, g, mm); break;
-                case 2: store<2>(acc, pc, k1, m, g, mm); break;
-                default: store<3>(acc, pc, k1, m, g, mm); break;
-            }
         }
     }
 };
@@ -250,32 +214,13 @@ __global__ __launch_bounds__(256) void softmax_grad_kernel(
             __syncthreads();        // the batch's reads are done before the next one is staged
         }
         double* __restrict__ pc = part + c * P;
-        lsum = wave_sum(lsum);      // the lanes with g > 0 add zeros
+        lsum = osum::wave_sum_asc(lsum);    // the lanes with g > 0 add zeros
         if (lane == 0) wl[wave] = lsum;
         __syncthreads();
         if (tid == 0) pc[0] = ((wl[0] + wl[1]) + wl[2]) + wl[3];
-        L::finish(acc, red, wave, lane, pc, k1, m, g, mm);
+        L::template finish<L>(acc, red, wave, lane, pc, k1, m, g, mm);
         __syncthreads();            // wl and red may be written again
     }
-}
-
-// part [nchunk, P] -> out [P]: every element the sum of its chunk partials in chunk order
-__global__ __launch_bounds__(256) void softmax_merge_kernel(int64_t P, int64_t nchunk,
-                                                            const double* __restrict__ part,
-                                                            double* __restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= P) return;
-    double s = part[e];
-    int64_t c = 1;
-    for (; c + 8 <= nchunk; c += 8) {       // eight loads in flight, added in chunk order
-        double t[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) t[u] = part[(c + u) * P + e];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += t[u];
-    }
-    for (; c < nchunk; ++c) s += part[c * P + e];
-    out[e] = s;
 }
 
 // img: one block of NT tiles in the image order of dense64_mfma.h, [ndch][u][NT][g][mm][s]
@@ -336,7 +281,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(
                     for (int q = 0; q < 4; ++q) e[t][q] = acc[t][q] - sd * dd[t][q];
                 }
                 const double lse = row_lse<TW>(e, k1, g);
-                const double v = wave_sum(g == 0 ? (lse - (ecy - sd * dy)) * wi : 0.0);
+                const double v = osum::wave_sum_asc(g == 0 ? (lse - (ecy - sd * dy)) * wi : 0.0);
                 if (lane == 0) ws[s][wave] = v;
             }
         } else {
@@ -359,7 +304,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(
                 }
             }
             ey = group_sum(ey);
-            const double v = wave_sum(g == 0 ? (lse - ey) * wi : 0.0);
+            const double v = osum::wave_sum_asc(g == 0 ? (lse - ey) * wi : 0.0);
             if (lane == 0) ws[0][wave] = v;
         }
         if (SEARCH || (mask & M_LOSS)) {
@@ -368,22 +313,6 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(
             __syncthreads();        // ws may be written again
         }
     }
-}
-
-// out [gridDim] = per step the sum of its nb batch partials, by a rule of nb alone
-__global__ __launch_bounds__(SM_RED) void softmax_sums_kernel(const double* __restrict__ part, int64_t nb,
-                                                              double* __restrict__ out) {
-    __shared__ double sh[SM_RED];
-    const double* __restrict__ p = part + (int64_t)blockIdx.x * nb;
-    double a = 0.0;
-    for (int64_t i = threadIdx.x; i < nb; i += SM_RED) a += p[i];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = SM_RED / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
 }
 
 template <int T, bool VEC, class... Args>
@@ -442,9 +371,7 @@ int alink_softmax_fused_grad_f64(const double* X, const double* y, const double*
     const unsigned blocks = (unsigned)(grid > 0 && grid < nchunk ? grid : nchunk);
     if (vec_ok(m, X)) launch_grad_t<true>(t, mt, blocks, st, X, y, w, n, m, k1, img, chunk_rows, nchunk, part);
     else launch_grad_t<false>(t, mt, blocks, st, X, y, w, n, m, k1, img, chunk_rows, nchunk, part);
-    const int64_t P = 1 + (int64_t)k1 * m;
-    hipLaunchKernelGGL(softmax_merge_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, P, nchunk, part,
-                       out);
+    osum::chunk_merge(osum::Identity{}, 1 + (int64_t)k1 * m, nchunk, part, out, st);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 
@@ -486,8 +413,7 @@ int alink_softmax_fused_rows_f64(const double* X, const double* y, const double*
         else ALINK_SM_ROWS(4, false);
     }
 #undef ALINK_SM_ROWS
-    if (search || (mask & M_LOSS))
-        hipLaunchKernelGGL(softmax_sums_kernel, dim3((unsigned)nsteps), dim3(SM_RED), 0, st, part, nb, out);
+    if (search || (mask & M_LOSS)) osum::batch_sums(part, nb, nsteps, out, st);
     return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 

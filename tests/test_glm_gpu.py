@@ -20,9 +20,10 @@ ALL = ("pred", "eta", "resid", "zw", "sums")
 COLS = ("eta", "pred", "z", "ww", "dres", "pres", "wres", "rres", "sums")
 KS, NS = (1, 2, 13, 14, 15, 30, 31, 126), (1, 3, 63, 64, 65, 200)
 # k and n taken in turn, the widest rows over several chunks as well, and k + 2 = 48, 64, 65, 96, 112: 3 .. 7 tiles,
-# where the deal of the tiles to the waves (t mod 4) is ragged
+# where the deal of the tiles to the waves (t mod 4) is ragged; at chunk_rows = 64, n = 513 and 641 are 9 and 11
+# chunks: the merge's round of eight loads in flight without a tail and with one of two
 GRAM_CASES = list(zip(KS, itertools.cycle(NS))) + [(126, 200), (31, 65), (46, 65), (62, 200), (63, 64), (94, 65),
-                                                    (110, 200)]
+                                                    (110, 200), (14, 513), (14, 641)]
 
 
 def dev_case(case):

@@ -30,6 +30,7 @@ def _sweep():
         add(k, 3)
         add(k, 128 if k <= 65 else 65, 200 if k <= 17 else 63)
     out += [(200, 17, 16), (200, 16, 33), (200, 5, 127), (200, 3, 128), (200, 2, 64)]
+    out += [(513, 5, 17), (641, 5, 17)]     # 9 and 11 chunks of 64 rows: the merge's round of eight loads in flight
     return sorted(set(out))
 
 
@@ -52,7 +53,7 @@ def test_em_step_matches_the_oracle(n, k, d):
     _lib.require()
     c = H.case(n, k, d)
     H.check_step(c, *_step(c), mirrored=True)
-    if n == 200:        # three full chunks and a tail of 8
+    if n >= 200:        # three full chunks and a tail of 8; 9 and 11 chunks
         H.check_step(c, *_step(c, chunk_rows=64), mirrored=True)
     pred, prob = _posterior(c, True)
     H.check_posterior(c, pred, prob)

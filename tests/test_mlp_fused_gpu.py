@@ -36,6 +36,13 @@ def test_gradient_and_loss_match_the_reference(n, layers):
     check_grad(*problem(n, layers, n + sum(layers), "cuda"), layers, chunk_rows=64)
 
 
+@pytest.mark.parametrize("n", [513, 641])
+def test_gradient_merges_nine_and_eleven_chunks(n):
+    """chunk_rows = 64: the merge's round of eight loads in flight, without a tail (9 chunks) and with one of two (11)."""
+    layers = [5, 7, 3]
+    check_grad(*problem(n, layers, n + sum(layers), "cuda"), layers, chunk_rows=64)
+
+
 @pytest.mark.parametrize("layers", [[17, 3], [5, 7, 3]], ids=str)
 def test_gradient_on_8_byte_aligned_rows_and_zero_weights(layers):
     X, y, w, coef = problem(131, layers, 3, "cuda")

@@ -17,9 +17,10 @@ U = L(2) ** -53
 DS, NS = (1, 2, 15, 16, 17, 127, 128, 129, 257, 1024), (1, 3, 63, 64, 65, 200)
 # d and n taken in turn, two and three blocks over several chunks as well, a last block of 3 .. 7 tiles, where the
 # deal of the tiles to the waves (t mod 4) is ragged, and 177: a full block, a last block of 4 tiles and the
-# off-diagonal unit between them
+# off-diagonal unit between them; at chunk_rows = 64, n = 513 and 641 are 9 and 11 chunks: the merge's round of eight
+# loads in flight without a tail and with one of two
 CASES = list(zip(DS, itertools.cycle(NS))) + [(129, 200), (257, 200), (33, 65), (49, 200), (65, 64), (81, 65),
-                                               (97, 200), (177, 200)]
+                                               (97, 200), (177, 200), (17, 513), (17, 641)]
 
 
 @functools.lru_cache(maxsize=None)

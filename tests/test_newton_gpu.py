@@ -23,8 +23,9 @@ from alink_amd.ops import _lib, newton as N  # noqa: E402
 pytestmark = pytest.mark.gpu
 DS, NS = (1, 2, 15, 16, 17, 33, 47, 48, 64, 65, 113, 128), (1, 3, 63, 64, 65, 200)
 # d and n taken in turn: every tile count 1 .. 8, the row-split rule at one and two tiles, odd d (scalar loads) and the
-# ragged deal of the tiles to the waves; the widest rows and 7 tiles over several chunks as well
-CASES = list(zip(DS, itertools.cycle(NS))) + [(128, 200), (97, 65)]
+# ragged deal of the tiles to the waves; the widest rows and 7 tiles over several chunks as well; at chunk_rows = 64,
+# n = 513 and 641 are 9 and 11 chunks: the merge's round of eight loads in flight without a tail and with one of two
+CASES = list(zip(DS, itertools.cycle(NS))) + [(128, 200), (97, 65), (17, 513), (17, 641)]
 
 
 SM_CASES = [(1, 1), (2, 3), (3, 16), (4, 17), (9, 33), (7, 128), (8, 128), (16, 64), (63, 16), (64, 16)]
@@ -68,10 +69,12 @@ def test_every_loss(code, k):
     check(run(case), H.oracle(case))
 
 
-@pytest.mark.parametrize("k1,m,n,chunk_rows", [c + (65, 0) for c in SM_CASES] + [(9, 33, 200, 64)])
+@pytest.mark.parametrize("k1,m,n,chunk_rows", [c + (65, 0) for c in SM_CASES]
+                         + [(9, 33, 200, 64), (9, 33, 513, 64), (9, 33, 641, 64)])
 def test_softmax_sums_against_the_oracle(k1, m, n, chunk_rows):
     """H (every block, exactly symmetric as a whole), G and the sums of the softmax pass: one to four class tiles, one
-    to eight dim tiles, one pair and many pairs per unit, a last group that is not full, several chunks."""
+    to eight dim tiles, one pair and many pairs per unit, a last group that is not full, several chunks (4, and 9 and
+    11: the merge's round of eight loads in flight)."""
     _lib.require()
     case = H.softmax_case(n, m, k1, seed=100 * k1 + m)
     check(run(case, chunk_rows=chunk_rows), H.softmax_oracle(case))

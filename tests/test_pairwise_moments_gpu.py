@@ -15,8 +15,9 @@ L = np.longdouble
 U = L(2) ** -53
 DS, NS = (1, 2, 15, 16, 17, 63, 64, 65, 81, 97, 129, 1024), (1, 3, 63, 64, 65, 200)
 # d and n taken in turn (one tile, a ragged tile, a full block of 64, a last block of 1 .. 4 tiles), then several
-# chunks over a full and a ragged block, their off-diagonal unit, and 177: two full blocks and a last one of 4 tiles
-CASES = list(zip(DS, itertools.cycle(NS))) + [(65, 200), (129, 200), (177, 200)]
+# chunks over a full and a ragged block, their off-diagonal unit, and 177: two full blocks and a last one of 4 tiles;
+# at chunk_rows = 64, n = 513 and 641 are 9 and 11 chunks: the merge's round of eight loads in flight
+CASES = list(zip(DS, itertools.cycle(NS))) + [(65, 200), (129, 200), (177, 200), (17, 513), (17, 641)]
 # at d = 1024 two combinations that share nothing; the others repeat them at the cost of a longdouble oracle each
 COMBOS = [(d, n, c, s, p) for (d, n), c, s, p in itertools.product(CASES, (0, 64), (False, True),
                                                                   ("none", "random", "structured"))

@@ -61,14 +61,34 @@ def _check(name, got, old, want, bound):
 @pytest.mark.parametrize("n,m,k1,kind", [
     (1, 1, 1, ""), (63, 16, 16, ""), (65, 17, 17, ""), (257, 33, 64, ""), (257, 128, 64, ""), (65, 128, 1, ""),
     (63, 1, 64, ""), (257, 17, 16, ""), (257, 33, 17, ""), (257, 16, 17, "offset"), (257, 33, 16, "zero_w")])
-def test_fused_grad_matches_reference(n, m, k1, kind):
+def test_fused_grad_matches_reference(n, m, k1, kind, chunk_rows=256):
     d = _data(n, m, k1, kind)
-    G, loss = F.fused_grad(d["X"], d["y"], d["w"], d["W"], chunk_rows=256)
+    G, loss = F.fused_grad(d["X"], d["y"], d["w"], d["W"], chunk_rows=chunk_rows)
     G0, loss0 = F.fused_grad_torch(d["X"], d["y"], d["w"], d["W"])
     assert G.shape == (k1, m)
     tag = f"grad n={n} m={m} k1={k1} {kind}"
     _check(tag + " G", G, G0, d["r"].T @ d["Xl"], n * EPS * (np.abs(d["r"]).T @ np.abs(d["Xl"])))
     _check(tag + " loss", loss, loss0, d["wloss"].sum(), n * EPS * np.abs(d["wloss"]).sum())
+
+
+@pytest.mark.parametrize("n", [513, 641])
+def test_fused_grad_merges_nine_and_eleven_chunks(n):
+    """chunk_rows = 64: the merge's round of eight loads in flight, without a tail (9 chunks) and with one of two (11)."""
+    test_fused_grad_matches_reference(n, 17, 17, "", chunk_rows=64)
+
+
+@pytest.mark.parametrize("n", [64 * 1024 + 1, 64 * 8192 + 1])
+def test_loss_sums_of_many_batches_match_reference(n):
+    """nb = 1025 and 8193 batch partials per series: a thread of the batch sums adds a second partial, and a first
+    round of eight loads in flight with one partial behind it."""
+    d = _data(n, 1, 1)
+    X, y, w, W, D = d["X"], d["y"], d["w"], d["W"], d["D"]
+    beta, nsteps = 0.37, 3
+    want = np.stack([d["ref"](d["Wn"].astype(L) - s * (beta * d["Dn"].astype(L)))[1] for s in range(nsteps)])
+    _check(f"sums n={n} search", F.search_losses(X, y, w, W, D, beta, nsteps),
+           F.search_losses_torch(X, y, w, W, D, beta, nsteps), want.sum(1), n * EPS * np.abs(want).sum(1))
+    _check(f"sums n={n} loss", F.rows(X, y, w, W, ("loss",))["loss"], F.rows_torch(X, y, w, W, ("loss",))["loss"],
+           d["wloss"].sum(), n * EPS * np.abs(d["wloss"]).sum())
 
 
 @pytest.mark.parametrize("n,m,k1,nsteps,kind", [
